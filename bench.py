@@ -19,6 +19,12 @@ n × (k·L + k + L) for the n coded pieces (benches/full_rlnc_encoder.rs:111-113
 Those counters charge the source k·L once per coded piece although one pass serves all n, so `value` is not
 bytes moved: `breakdown.roundtrip_goodput_GiBps` (source bytes through encode + decode) sits beside it, and the
 roofline is the kernel's own: GF(2^8) multiply-adds/s against the measured XOR3-issue ceiling (measure/).
+A plain run (`--gpus 1 --steps K --warmup W`) sets up, lets the clocks settle (~50 ms of launch groups), runs W
+untimed and K timed steps and prints the line with `value` and `ms_per_step`.  `--full` adds everything else to the
+line: the decoded objects verified against the source, `breakdown`, both rooflines (their per-part times are read
+from those launch groups, their ceilings come from measure/), `hbm_single_pass_encode` and the CPU baselines.
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (inputs are seeded: the same
+arguments give the same arrays).
 Multi-GPU: objects are sharded across ranks, no data-path collective; the only collectives are the timing barrier
 and the max/sum reductions of the result.  `--gpus N` without a launcher (WORLD_SIZE unset) starts N rank
 processes itself (fresh interpreters, before any GPU call) with the same arguments.
@@ -177,6 +183,31 @@ def timed_loop(step, steps: int, warmup: int, dist: Dist, sync) -> float:
     sync()
     elapsed = time.perf_counter() - t0
     return dist.allreduce(elapsed, "max")
+
+
+DUMP_SAMPLE = 4 << 20  # bytes sampled from each large output array: two float32 files of 16 MiB, under the 64 MB limit
+DUMP_SEED = 0x44554D50
+
+
+def sample_index(numel: int, size: int, seed: int):
+    """--dump-outputs: the flat positions sampled from an array of `numel` bytes (sorted, fixed by the seed alone, so
+    two runs with the same arguments sample the same bytes); None when the array is written whole."""
+    import numpy as np
+
+    if numel <= size:
+        return None
+    return np.sort(np.random.default_rng(seed).integers(0, numel, size, dtype=np.int64))
+
+
+def write_outputs(path: str, dist: Dist, arrays: dict) -> None:
+    """--dump-outputs: one DIR/<name>.npy per array (rank r > 0 of a multi-rank run writes <name>_rank<r>.npy)."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    suffix = f"_rank{dist.rank}" if dist.rank else ""
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), name
+        np.save(os.path.join(path, name + suffix + ".npy"), a)
 
 
 def _free_port() -> int:
@@ -345,6 +376,16 @@ def parse_args(argv=None):
                          "a fixed job split over the ranks")
     ap.add_argument("--objects", type=int, default=None,
                     help="config2: objects per GPU per step (32: profiles/r01_launch_size.txt); config5: the whole job")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: the decoded objects verified against the source, the "
+                         "per-part times from --breakdown-steps launch groups run before the timed loop, the encode "
+                         "and decode rooflines with the live ceilings, the single-pass HBM encode and the CPU "
+                         "baselines (--no-cpu-baseline, --no-ceiling and --cpu-* trim it).  Without it a run sets up, "
+                         "warms up, times the steps and prints metric / value / ms_per_step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step left in its output buffers (coded "
+                         "pieces, decoded objects, statuses, lengths) as DIR/<name>.npy, float32/float64; the large "
+                         "arrays as a fixed seeded sample of their bytes (sample_index) beside the byte sum of every row")
     ap.add_argument("--k", type=int, default=None)
     ap.add_argument("--piece-bytes", type=int, default=None)
     ap.add_argument("--coded", type=int, default=None)
@@ -434,6 +475,8 @@ def run_oracle_cpu(args, dist: Dist):
     total_objs = dist.allreduce(float(B), "sum")
     ok_rank = dist.allgather(float(all(np.array_equal(last[o], src[o]) for o in range(B))))
     ok = all(v == 1.0 for v in ok_rank)
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, dist, {"decoded": np.stack(last).astype(np.float32)})
     if dist.rank == 0:
         print(json.dumps({"metric": METRIC, "value": round(total / elapsed / GIB, 6), "unit": "GiB/s",
                           "n_gpus": dist.world, "world_size_initialised": dist.initialised_world(),
@@ -484,20 +527,22 @@ def run_gpu(args, dist: Dist):
                                                                                  dtype=np.uint8)).to(dev)
 
     def buffers(B):
-        return dict(pieces=torch.empty((B, n, k + L), dtype=torch.uint8, device=dev),
+        # zeroed once, so a byte the step does not write (a rank-deficient object's rows) reads the same in every run
+        return dict(pieces=torch.zeros((B, n, k + L), dtype=torch.uint8, device=dev),
                     # the encode's code-block address stream, written ahead on the side stream (encode_batch_prepare)
                     plan=torch.empty(batch.encode_plan_bytes(k, B, n), dtype=torch.uint8, device=dev),
                     # the decode's T x data address stream, written on the side stream behind the elimination
                     dplan=torch.empty(batch.decode_apply_plan_bytes(k, m, B), dtype=torch.uint8, device=dev),
-                    decoded=torch.empty((B, k, L), dtype=torch.uint8, device=dev),
-                    pst=torch.empty((B, m), dtype=torch.int32, device=dev),
-                    ost=torch.empty(B, dtype=torch.int32, device=dev),
-                    dl=torch.empty(B, dtype=torch.int64, device=dev),
+                    decoded=torch.zeros((B, k, L), dtype=torch.uint8, device=dev),
+                    pst=torch.zeros((B, m), dtype=torch.int32, device=dev),
+                    ost=torch.zeros(B, dtype=torch.int32, device=dev),
+                    dl=torch.zeros(B, dtype=torch.int64, device=dev),
                     T=torch.empty((B, k, m), dtype=torch.uint8, device=dev),
                     rank=torch.empty(B, dtype=torch.int32, device=dev),
-                    obj=(0, 0))
+                    obj=(0, 0), seq=-1)
 
     sets = [buffers(C)]
+    launched = [0]  # launch groups started so far; a set's "seq" is the number of the last group that wrote it
     enc_events, dec_events, apply_events, plan_events = [], [], [], []
     ctx_side = rlnc_amd.Context(device) if args.pipeline else None
     if ctx_side is not None:
@@ -570,6 +615,8 @@ def run_gpu(args, dist: Dist):
                 batch.decode_batch_device(received, k, decoded, pst, ost, dl, ctx)
         e2.record()
         S["obj"] = (c0, c1)
+        S["seq"] = launched[0]
+        launched[0] += 1
         enc_events.append((e0, e1))
         dec_events.append((e1, e2))
 
@@ -632,6 +679,8 @@ def run_gpu(args, dist: Dist):
                     batch.decode_batch_apply_planned(rec, k, T, rank, decoded, ost, dl, S["dplan"], ctx_dec)
                 ev_done[bi].record()
             S["obj"] = (c0, c1)
+            S["seq"] = launched[0]
+            launched[0] += 1
 
         def step_pipelined():
             for c0, c1 in chunks:
@@ -656,7 +705,10 @@ def run_gpu(args, dist: Dist):
     elif pipelined:
         # the per-part times (encode launch for the roofline, decode) come from pipeline-1 launch groups run
         # before the timed loop (the first 6 discarded: clocks and caches settle): a kernel's own duration, not
-        # its overlap with the next group's kernels
+        # its overlap with the next group's kernels.  A plain run launches the same groups (~50 ms) and reads no
+        # times from them: the headline has always been measured behind them, and without them the timed steps
+        # of `--warmup 5` start before the clocks have settled and run 2-3 % slower (interleaved A/B; 35 warmup
+        # steps in their place recover most of it)
         for i in range(args.breakdown_steps + 6):
             c0, c1 = chunks[i % len(chunks)]
             launch_serial(c0, c1, sets[0], isolate=True)
@@ -664,6 +716,83 @@ def run_gpu(args, dist: Dist):
         skip = 6
     elapsed = timed_loop(run, args.steps, args.warmup, dist, torch.cuda.synchronize)
     torch.cuda.synchronize()
+
+    per_rank_bytes = step_bytes(objs, k, L, n) if not args.encode_only else objs * n * encode_counter(k, L)
+    total_bytes = dist.allreduce(float(per_rank_bytes * args.steps), "sum")
+    total_objs = dist.allreduce(float(objs), "sum")
+    value = total_bytes / elapsed / GIB
+    variant = VARIANTS[args.variant]
+    headline = {
+        "metric": METRIC,
+        "value": round(value, 2),
+        "unit": "GiB/s",
+        "n_gpus": dist.world,
+        "world_size_initialised": dist.initialised_world(),
+        "process_group_backend": dist.backend(),
+        "device_per_rank": [int(v) for v in dist.allgather(float(device))],
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
+        "higher_is_better": True,
+        "scaling": wl["scaling"],
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic: uniform random source bytes (torch generator, seeded per rank), coefficients "
+                "uniform bytes from a seeded host RNG",
+        "config": {
+            "workload": (f"configs[1]+[2]: per object encode k={k} x {L} B -> {n} coded pieces + decode from the "
+                         f"first {m}; {objs} objects per GPU per step") if args.workload == "config2" else
+                        (f"configs[4]: {int(total_objs)} objects x k={k} x {L} B split over {dist.world} rank(s) "
+                         f"({objs} on rank {dist.rank}), encode {n} coded + decode {m} per object, "
+                         f"launches of {C} objects; one step = the whole job"),
+            "k": k, "piece_bytes": L, "coded_per_object": n, "decoded_from": m, "objects_per_gpu": objs,
+            "objects_total": int(total_objs), "objects_per_launch": C,
+            "parallelism": f"objects sharded over {dist.world} rank(s), no data-path collective",
+            "kernel_variant": variant,
+            "encode_address_stream": "launch stream (--no-plan)" if args.no_plan else
+                                     "written ahead on the side stream (rlnc_encode_batch_prepare)",
+            "pipeline": {0: "serial", 1: "elimination on a side stream concurrent with the encode data work",
+                         2: "elimination beside the encode data work, and launch group i+1's encode beside group "
+                            "i's decode (two buffer sets)"}[1 if args.pipeline == 2 and not pipelined else args.pipeline]
+                        + (", replayed as one captured HIP graph per step" if args.graph else ""),
+        },
+    }
+
+    if args.dump_outputs:
+        # what the last timed step left in its output buffers: the launch groups of that step whose buffer set no
+        # later group has reused (config2: the step's one group), in object order.  The coded pieces and the decoded
+        # objects as a seeded sample of their bytes and, over every byte, the sum of each piece / decoded row
+        live = sorted((S for S in sets if S["seq"] >= launched[0] - len(chunks)), key=lambda S: S["seq"])
+        arrays = {name: [] for name in ("objects", "pieces", "pieces_rowsum", "decoded", "decoded_rowsum",
+                                        "piece_status", "object_status", "decoded_len")}
+
+        def sampled(t, g):
+            flat = t.reshape(-1)
+            # the sample is shared among the step's live groups and the ranks: all files together stay under 64 MB
+            idx = sample_index(flat.numel(), DUMP_SAMPLE // (len(live) * dist.world), DUMP_SEED + g)
+            if idx is not None:
+                flat = flat[torch.from_numpy(idx).to(dev)]
+            return flat.to(torch.float32).cpu().numpy()
+
+        for g, S in enumerate(live):
+            c0, c1 = S["obj"]
+            b = c1 - c0
+            arrays["objects"].append(np.arange(c0, c1, dtype=np.float64))
+            arrays["pieces"].append(sampled(S["pieces"][:b], g))
+            arrays["pieces_rowsum"].append(S["pieces"][:b].sum(dim=2, dtype=torch.int64).double().cpu().numpy())
+            if not args.encode_only:
+                arrays["decoded"].append(sampled(S["decoded"][:b], g))
+                arrays["decoded_rowsum"].append(S["decoded"][:b].sum(dim=2, dtype=torch.int64).double().cpu().numpy())
+                arrays["piece_status"].append(S["pst"][:b].to(torch.float32).cpu().numpy())
+                arrays["object_status"].append(S["ost"][:b].to(torch.float32).cpu().numpy())
+                arrays["decoded_len"].append(S["dl"][:b].double().cpu().numpy())
+        write_outputs(args.dump_outputs, dist, {name: np.concatenate(v) for name, v in arrays.items() if v})
+
+    if not args.full:
+        if dist.rank == 0:
+            print(json.dumps(headline), flush=True)
+        dist.close()
+        return
 
     def verified(S):
         # every full-rank object of the last launch group that used this set decodes to its source
@@ -698,11 +827,6 @@ def run_gpu(args, dist: Dist):
     enc_ms_rank = dist.allgather(enc_ms)
     dec_ms_rank = dist.allgather(dec_ms)
 
-    per_rank_bytes = step_bytes(objs, k, L, n) if not args.encode_only else objs * n * encode_counter(k, L)
-    total_bytes = dist.allreduce(float(per_rank_bytes * args.steps), "sum")
-    total_objs = dist.allreduce(float(objs), "sum")
-    value = total_bytes / elapsed / GIB
-
     # roofline of the dominant kernel (the encode matmul, one launch per launch group) from HIP events.  The
     # kernel is bound by VALU issue, not HBM: `achieved` = its GF(2^8) multiply-adds per second,
     # `peak` = the live XOR3-issue ceiling of the bit-sliced design; the HBM view (compulsory bytes: source once
@@ -712,7 +836,6 @@ def run_gpu(args, dist: Dist):
     achieved = ma_per_launch / (enc_ms * 1e-3) / 1e12
     enc_alg = B * n * encode_counter(k, L)           # reference-counter bytes per launch
     enc_compulsory = B * (k * L + n * (k + L))       # source read once + coded pieces written
-    variant = VARIANTS[args.variant]
     traffic, traffic_src = pmc_traffic(variant, B, k, L, n)
     # the product kernel alone is inside e0..e1 unless --no-plan puts the address launch in front of it
     enc_kernel = KERNELS[variant] if args.no_plan else KERNELS[variant].replace("bsj_offset_kernel + ", "")
@@ -828,45 +951,13 @@ def run_gpu(args, dist: Dist):
             single["frac_of_pattern_ceiling"] = round(read1 / ms1 / 1e6 / hc["pattern_read_GBps"], 4)
 
     result = {
-        "metric": METRIC,
-        "value": round(value, 2),
-        "unit": "GiB/s",
-        "n_gpus": dist.world,
-        "world_size_initialised": dist.initialised_world(),
-        "process_group_backend": dist.backend(),
+        **headline,
         "verified_per_rank": [bool(v) for v in ok_rank],
         "kernel_ms_per_rank": [round(v, 4) for v in enc_ms_rank],
         "decode_ms_per_rank": [round(v, 4) for v in dec_ms_rank],
         # 1: the device runs 16-byte vector memory instructions at any byte address (probed at context creation;
         # misaligned rows take the vector kernels directly), 0: they go through realigning copies
         "unaligned_vector_access": int(ctx.lib.rlnc_device_unaligned_vector_access(device)),
-        "device_per_rank": [int(v) for v in dist.allgather(float(device))],
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 4),
-        "higher_is_better": True,
-        "scaling": wl["scaling"],
-        "vs_baseline": None,
-        "dtype": "u8",
-        "data": "synthetic: uniform random source bytes (torch generator, seeded per rank), coefficients "
-                "uniform bytes from a seeded host RNG",
-        "config": {
-            "workload": (f"configs[1]+[2]: per object encode k={k} x {L} B -> {n} coded pieces + decode from the "
-                         f"first {m}; {objs} objects per GPU per step") if args.workload == "config2" else
-                        (f"configs[4]: {int(total_objs)} objects x k={k} x {L} B split over {dist.world} rank(s) "
-                         f"({objs} on rank {dist.rank}), encode {n} coded + decode {m} per object, "
-                         f"launches of {C} objects; one step = the whole job"),
-            "k": k, "piece_bytes": L, "coded_per_object": n, "decoded_from": m, "objects_per_gpu": objs,
-            "objects_total": int(total_objs), "objects_per_launch": C,
-            "parallelism": f"objects sharded over {dist.world} rank(s), no data-path collective",
-            "kernel_variant": variant,
-            "encode_address_stream": "launch stream (--no-plan)" if args.no_plan else
-                                     "written ahead on the side stream (rlnc_encode_batch_prepare)",
-            "pipeline": {0: "serial", 1: "elimination on a side stream concurrent with the encode data work",
-                         2: "elimination beside the encode data work, and launch group i+1's encode beside group "
-                            "i's decode (two buffer sets)"}[1 if args.pipeline == 2 and not pipelined else args.pipeline]
-                        + (", replayed as one captured HIP graph per step" if args.graph else ""),
-        },
         "roofline": roofline,
         "roofline_decode": roofline_decode,
         "hbm_single_pass_encode": single,

@@ -2,12 +2,12 @@
 """The rocprofv3 durations of exactly the launches bench.py's rooflines time (roofline.kernel_ms, and with --decode
 roofline_decode.kernel_ms).
 
-bench.py (default --pipeline 2) runs --breakdown-steps + 6 launch groups of the pipeline-1 form BEFORE its warmup and
+bench.py --full (default --pipeline 2) runs --breakdown-steps + 6 launch groups of the pipeline-1 form BEFORE its warmup and
 timed steps, and averages the HIP-event windows of all but the first 6.  Those are the first launches of the program
 of the encode product (gf_matmul_bsj_kernel<8, true> at the encode grid) and of the decode's T x data product
 (gf_matmul_bsj_kernel<4, true> at the decode grid: its 32-row tiles), so this selects launches [skip, skip + steps) of
 that kernel at its most frequent grid, in start order, from the rocpd database of
-`rocprofv3 --kernel-trace --stats -- python bench.py ...` and compares their average with the bench line of the same
+`rocprofv3 --kernel-trace --stats -- python bench.py --full ...` and compares their average with the bench line of the same
 run.  With --decode the decode apply's other launches in the same groups (its address launch and the marker scan) are
 averaged too, so the product + them can be set against roofline_decode.kernel_ms (events around the whole apply).
 

@@ -18,7 +18,7 @@ for pass in $(seq 1 ${PASSES:-2}); do
       rc=$?; echo "$v parity rc=$rc $(tail -1 $OUT/bsj_t_$v.log)"
       if [ $rc -ne 0 ]; then break 2; fi
     fi
-    timeout -k 10 300 python bench.py --steps 30 --no-cpu-baseline --no-ceiling > $OUT/bsj_b.json 2>/dev/null
+    timeout -k 10 300 python bench.py --full --steps 30 --no-cpu-baseline --no-ceiling > $OUT/bsj_b.json 2>/dev/null
     rc=$?; if [ $rc -ne 0 ]; then echo "$v bench rc=$rc"; break 2; fi
     python -c "
 import json; d=json.load(open('$OUT/bsj_b.json')); b=d['breakdown']

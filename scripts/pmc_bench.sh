@@ -13,7 +13,7 @@ i=0
 for group in FETCH_SIZE WRITE_SIZE ${EXTRA_GROUPS:-}; do
   i=$((i+1))
   timeout -k 10 -s KILL 120 rocprofv3 --kernel-trace --pmc ${group//,/ } -d "$OUT/p$i" -o run --output-format csv -- \
-      python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/p$i.log" 2>&1
+      python3 "$ROOT/bench.py" --full --steps 3 --warmup 1 --no-cpu-baseline ${BENCH_ARGS:-} > "$OUT/p$i.log" 2>&1
   rc=$?; echo "pmc pass $i ($group) rc=$rc"
   [ $rc -ne 0 ] && exit $rc
 done

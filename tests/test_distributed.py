@@ -171,6 +171,37 @@ def test_single_rank_initialises_a_group():
     assert res["n_gpus"] == 1 and res["world_size_initialised"] == 1
 
 
+def test_full_is_off_by_default_and_steps_are_the_timed_steps():
+    import bench
+
+    a = bench.parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs is None and (a.steps, a.warmup) == (7, 2)
+    assert bench.parse_args(["--full"]).full is True
+    calls = []
+    bench.timed_loop(lambda: calls.append(1), steps=7, warmup=2, dist=bench.Dist(), sync=lambda: None)
+    assert len(calls) == 9
+
+
+def test_dump_outputs_writes_the_last_steps_arrays(tmp_path):
+    """--dump-outputs through the oracle harness: float32 arrays of the last step's decoded objects (rank 0's
+    generator: seed 100, 3 objects of k = 8 x 512 bytes), the same in every run; the sample positions of a large
+    array depend on the seed alone."""
+    import numpy as np
+
+    import bench
+
+    line = _line(["--workload", "oracle-cpu", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path)])
+    assert line["steps"] == 2 and line["ms_per_step"] > 0
+    assert os.listdir(tmp_path) == ["decoded.npy"]
+    got = np.load(tmp_path / "decoded.npy")
+    want = np.random.default_rng(100).integers(0, 256, (3, 8, 512), dtype=np.uint8)
+    assert got.dtype == np.float32 and np.array_equal(got, want.astype(np.float32))
+    idx = bench.sample_index(1 << 31, 1000, 5)
+    assert np.array_equal(idx, bench.sample_index(1 << 31, 1000, 5)) and idx.size == 1000
+    assert (np.diff(idx) >= 0).all() and idx.min() >= 0 and idx.max() < 1 << 31
+    assert bench.sample_index(1000, 1000, 5) is None  # small arrays are written whole
+
+
 def _line(args):
     import json
     import subprocess

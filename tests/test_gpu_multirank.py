@@ -51,8 +51,8 @@ def check_common(line, n=2):
 @pytest.mark.timeout(400)
 def test_two_ranks_config2_weak():
     objs = 4
-    line = run_bench(["--gpus", "2", "--objects", str(objs), "--steps", "3", "--warmup", "1", "--breakdown-steps", "4",
-                      "--no-cpu-baseline", "--no-ceiling"])
+    line = run_bench(["--full", "--gpus", "2", "--objects", str(objs), "--steps", "3", "--warmup", "1",
+                      "--breakdown-steps", "4", "--no-cpu-baseline", "--no-ceiling"])
     check_common(line)
     assert line["scaling"] == "weak"
     assert line["config"]["objects_per_gpu"] == objs
@@ -65,8 +65,8 @@ def test_two_ranks_config2_weak():
 @pytest.mark.timeout(400)
 def test_two_ranks_config5_strong_split():
     job = 33  # odd: rank 0 takes 17, rank 1 takes 16
-    line = run_bench(["--gpus", "2", "--workload", "config5", "--objects", str(job), "--chunk", "8", "--steps", "2",
-                      "--warmup", "1", "--breakdown-steps", "2", "--no-cpu-baseline", "--no-ceiling"])
+    line = run_bench(["--full", "--gpus", "2", "--workload", "config5", "--objects", str(job), "--chunk", "8",
+                      "--steps", "2", "--warmup", "1", "--breakdown-steps", "2", "--no-cpu-baseline", "--no-ceiling"])
     check_common(line)
     assert line["scaling"] == "strong"
     assert line["config"]["objects_total"] == job  # the split covers every object of the fixed job exactly once
@@ -79,8 +79,8 @@ def test_four_ranks_config5_strong_split():
     """Four ranks on the lease's GPU (profiles/r06_config5_n4_onegpu.json is the full job the same way): the ragged
     split (35 = 9 + 9 + 9 + 8) covers the job once and every rank verifies its share."""
     job = 35
-    line = run_bench(["--gpus", "4", "--workload", "config5", "--objects", str(job), "--chunk", "8", "--steps", "2",
-                      "--warmup", "1", "--breakdown-steps", "2", "--no-cpu-baseline", "--no-ceiling"])
+    line = run_bench(["--full", "--gpus", "4", "--workload", "config5", "--objects", str(job), "--chunk", "8",
+                      "--steps", "2", "--warmup", "1", "--breakdown-steps", "2", "--no-cpu-baseline", "--no-ceiling"])
     check_common(line, n=4)
     assert line["scaling"] == "strong"
     assert line["config"]["objects_total"] == job
