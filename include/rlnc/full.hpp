@@ -249,6 +249,22 @@ class Decoder {
         if (r.is_err()) return r.error();
         return Decoder(h);
     }
+    // A decoder in a rank mode (rlnc_hip.h, "Rank mode"): RLNC_RANK_MODE_REFERENCE is create() above;
+    // RLNC_RANK_MODE_TRUE answers PieceNotUseful exactly for linearly dependent pieces -- not the crate's behaviour on
+    // sparse or structured coding vectors.  The decoder snapshots the mode; the thread's context is left as it was.
+    static Result<Decoder> create(size_t piece_byte_len, size_t required_piece_count, int rank_mode) {
+        rlnc_context *c = detail::context();
+        const int before = rlnc_get_rank_mode(c);
+        if (rlnc_set_rank_mode(c, rank_mode) != RLNC_OK)
+            throw DeviceError(std::string("rlnc_set_rank_mode: ") + rlnc_last_error());
+        rlnc_decoder *h = nullptr;
+        const int s = rlnc_decoder_new(c, piece_byte_len, required_piece_count, &h);
+        rlnc_set_rank_mode(c, before);
+        auto r = detail::status(s);
+        if (r.is_err()) return r.error();
+        return Decoder(h);
+    }
+    int rank_mode() const { return rlnc_decoder_get_rank_mode(h_.h); }
     Result<void> decode(const std::vector<uint8_t> &piece) {  // decoder.rs:96-118
         return detail::status(rlnc_decoder_decode(h_.h, piece.data(), piece.size()));
     }

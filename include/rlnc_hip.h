@@ -34,6 +34,20 @@
  *     context's workspace addresses: they are frozen, and a later call that would need a larger workspace
  *     fails with RLNC_ERR_INVALID_ARGUMENT instead of moving them (run the largest shape eagerly before
  *     capturing, or use another context for other shapes).
+ *   - Rank mode.  RLNC_RANK_MODE_REFERENCE (0, the default) replays the crate's DecoderMatrix::rref bit for bit,
+ *     including its quirk: it pivots only on the diagonal, so sparse or structured coding vectors can be counted
+ *     useful when they are linearly dependent.  RLNC_RANK_MODE_TRUE (1) is NOT the crate's
+ *     behaviour on such input: the decoder keeps the useful pieces' rows [c | e] (c: k coefficient bytes, e: one
+ *     byte per received-piece slot) in reduced row-echelon form with free pivot columns.  Pushing piece p with
+ *     coefficients h: (1) rank == k answers ReceivedAllPieces and changes nothing; (2) v = [h | unit(p)], and for
+ *     every stored row i, v ^= h[pivot_i] · row_i; (3) v[0:k] all zero answers PieceNotUseful and changes nothing;
+ *     (4) pc = first nonzero column of v, v is scaled by 1 / v[pc], every stored row gets row_i ^= row_i[pc] · v,
+ *     and v is stored with pivot pc: Ok.  rank = number of rows; T row r (r < rank) is the e part of the row with
+ *     the r-th smallest pivot column, rows >= rank are zero.  A piece is therefore useful exactly when it is
+ *     independent of the useful pieces before it; at rank k, T × data is the source as in mode 0.  On dense random
+ *     coefficients the two modes answer alike.  The device kernel of mode 1 applies when
+ *     8192 + 4·(k·D + 2·D + m·ceil(k/4) + m + 2·k + ceil(k/4)) <= 160 KiB with D = ceil(k/4) + ceil(m/4);
+ *     beyond that each call does what it does in mode 0 beyond LDS (host elimination, or the same error).
  */
 #ifndef RLNC_HIP_H
 #define RLNC_HIP_H
@@ -148,6 +162,15 @@ int rlnc_set_column_run(rlnc_context *ctx, int col_run);
  * and 2 use when it applies).  The A/B build adds 3 (clean state on LDS), 4 (one wave's registers) and 6 (the
  * round-1 multi-wave register path).  All are exact replicas; the switch exists for A/B tests. */
 int rlnc_set_decode_path(rlnc_context *ctx, int path);
+/* Rank mode of the context (see "Rank mode" above): governs rlnc_decode_batch, rlnc_decode_batch_device,
+ * rlnc_decode_batch_eliminate, rlnc_decode_ragged and rlnc_decode_host_stream, and is snapshotted by rlnc_decoder_new.
+ * Other values: RLNC_ERR_INVALID_ARGUMENT.  In mode 1 decode paths 0 and 2 use the true-rank device kernel when it
+ * fits, path 1 the host; path 5 (and the A/B build's 3, 4, 6) name reference-mode kernels and make the decode calls
+ * return RLNC_ERR_INVALID_ARGUMENT (no silent fallback). */
+#define RLNC_RANK_MODE_REFERENCE 0
+#define RLNC_RANK_MODE_TRUE 1
+int rlnc_set_rank_mode(rlnc_context *ctx, int mode);
+int rlnc_get_rank_mode(const rlnc_context *ctx); /* -1 for a null context */
 
 /* ---- Encoder: src/full/encoder.rs ----------------------------------------------------------------- */
 typedef struct rlnc_encoder rlnc_encoder;
@@ -204,6 +227,9 @@ typedef struct rlnc_decoder rlnc_decoder;
 int rlnc_decoder_new(rlnc_context *ctx, size_t piece_byte_len, size_t required_piece_count, rlnc_decoder **out);
 /* #[derive(Clone)] (decoder.rs:8): elimination state, counters and the received data rows are copied. */
 int rlnc_decoder_clone(const rlnc_decoder *dec, rlnc_decoder **out);
+/* The rank mode the decoder took from its context when it was created (a clone keeps it; a later
+ * rlnc_set_rank_mode on the context does not change it).  -1 for a null decoder. */
+int rlnc_decoder_get_rank_mode(const rlnc_decoder *dec);
 void rlnc_decoder_free(rlnc_decoder *dec);
 /* Decoder::decode (decoder.rs:96-118): Ok / PieceNotUseful / ReceivedAllPieces / InvalidPieceLength.
  * The accept/reject answer is immediate (exact replica of the diagonal-pivot RREF on the coefficient
@@ -390,6 +416,9 @@ int rlnc_decode_host_stream(rlnc_context *ctx, const uint8_t *pieces, size_t pie
  * fixed_slots > 0: piece p owns E column p; 0: columns are recycled once unreferenced. */
 typedef struct rlnc_elimination rlnc_elimination;
 int rlnc_elimination_new(size_t k, size_t fixed_slots, rlnc_elimination **out);
+/* The same engine in a rank mode (rlnc_elimination_new is mode 0).  In mode 1 a piece that is not useful keeps no slot
+ * (keep = 0), recycled slots never exceed k, and rlnc_elimination_coefficients returns the RREF rows in pivot order. */
+int rlnc_elimination_new_mode(size_t k, size_t fixed_slots, int rank_mode, rlnc_elimination **out);
 void rlnc_elimination_free(rlnc_elimination *e);
 /* Decoder::decode on the k coefficient bytes: Ok / PieceNotUseful / ReceivedAllPieces. */
 int rlnc_elimination_push(rlnc_elimination *e, const uint8_t *coeffs, int32_t *slot, int32_t *keep);

@@ -72,6 +72,8 @@ _SIGS = {
     "rlnc_set_kernel_variant": (C.c_int, [vp, C.c_int, C.c_int]),
     "rlnc_set_column_run": (C.c_int, [vp, C.c_int]),
     "rlnc_set_decode_path": (C.c_int, [vp, C.c_int]),
+    "rlnc_set_rank_mode": (C.c_int, [vp, C.c_int]),
+    "rlnc_get_rank_mode": (C.c_int, [vp]),
     "rlnc_encoder_new": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
     "rlnc_encoder_without_padding": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
     "rlnc_encoder_from_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
@@ -95,6 +97,7 @@ _SIGS = {
     "rlnc_decoder_new": (C.c_int, [vp, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
     "rlnc_decoder_clone": (C.c_int, [vp, C.POINTER(vp)]),
     "rlnc_decoder_free": (None, [vp]),
+    "rlnc_decoder_get_rank_mode": (C.c_int, [vp]),
     "rlnc_decoder_decode": (C.c_int, [vp, vp, C.c_size_t]),
     "rlnc_decoder_decode_device": (C.c_int, [vp, vp, C.c_size_t]),
     "rlnc_decoder_is_already_decoded": (C.c_int, [vp]),
@@ -140,6 +143,7 @@ _SIGS = {
     "rlnc_decode_host_stream": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp,
                                           i32p, i32p, u64p, C.c_size_t]),
     "rlnc_elimination_new": (C.c_int, [C.c_size_t, C.c_size_t, C.POINTER(vp)]),
+    "rlnc_elimination_new_mode": (C.c_int, [C.c_size_t, C.c_size_t, C.c_int, C.POINTER(vp)]),
     "rlnc_elimination_free": (None, [vp]),
     "rlnc_elimination_push": (C.c_int, [vp, vp, i32p, i32p]),
     "rlnc_elimination_rank": (C.c_size_t, [vp]),

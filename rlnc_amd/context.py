@@ -54,6 +54,18 @@ class Context:
         are exact."""
         check(self.lib.rlnc_set_decode_path(self.h, int(path)), self.lib)
 
+    def set_rank_mode(self, mode: int = 0):
+        """0 (default): the reference crate's diagonal-pivot elimination, replayed bit for bit (its rank over-count on
+        sparse or structured coding vectors included).  1: true rank -- a piece is useful exactly when it is linearly
+        independent of the useful pieces before it (not the crate's behaviour on such input).  Governs this context's
+        decode_batch / decode_batch_device / decode_batch_eliminate / decode_ragged / decode_host_stream calls and
+        the decoders created on it afterwards.  In mode 1 decode paths 3-6 are InvalidArgument."""
+        check(self.lib.rlnc_set_rank_mode(self.h, int(mode)), self.lib)
+
+    @property
+    def rank_mode(self) -> int:
+        return int(self.lib.rlnc_get_rank_mode(self.h))
+
     def set_kernel_variant(self, variant: int = 8, max_tile_rows: int = 0):
         """GF(2^8) matmul variant (include/rlnc_hip.h): 8 = bit-sliced, one code block per coefficient, plane
         combinations built once per workgroup and shared through LDS, 64-row tiles of 8 waves above 32 output

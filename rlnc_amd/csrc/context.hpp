@@ -16,6 +16,7 @@
 
 #include "../../include/rlnc_hip.h"
 #include "kernels.hpp"
+#include "rank_kernels.hpp"
 
 namespace rlnc::eng {
 
@@ -203,6 +204,19 @@ struct rlnc_context {
     int decode_path = 0;  // 0 auto (device when it fits LDS), 1 host elimination, 2 device elimination,
                           // 3 device elimination with the clean state on LDS, 4 ... on one wave's
                           // registers, 5 blocked clean run, 6 round-1 multi-wave registers (A/B)
+    int rank_mode = 0;  // RLNC_RANK_MODE_*: 0 the reference's diagonal-pivot replica, 1 true rank (rank.hip, elimination.hpp)
+    // the device elimination of this context's rank mode fits LDS
+    bool elim_fits(size_t k, size_t m) const {
+        return (rank_mode == RLNC_RANK_MODE_TRUE ? rlnc::rank_lds_bytes(int(k), int(m)) : rlnc::rref_lds_bytes(int(k), int(m))) <=
+               rlnc::kRrefMaxLds;
+    }
+    // decode paths 3-6 name reference-mode kernels: no silent fallback in true-rank mode
+    int rank_mode_path_check() const {
+        if (rank_mode == RLNC_RANK_MODE_TRUE && decode_path >= 3)
+            return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                             "decode path %d is a reference-mode kernel: rank mode 1 takes paths 0, 1 and 2", decode_path);
+        return RLNC_OK;
+    }
     // workspaces of the stream-ordered batch / _device API (one caller thread per context at a time)
     DevBuf ws_bsj;   // the small-object decode's block-offset stream, written by its elimination
     DevBuf ws_need;  // ... and its per-object "payload tail all zero" flags (RrefParams::tail_need)

@@ -98,8 +98,10 @@ const HostField &host_field() {
     return f;
 }
 
-Elimination::Elimination(size_t k, size_t fixed_slots) : k_(k), fixed_(fixed_slots > 0) {
-    cap_ = fixed_ ? fixed_slots : std::max<size_t>(k, 1) + 1;
+Elimination::Elimination(size_t k, size_t fixed_slots, int rank_mode)
+    : k_(k), fixed_(fixed_slots > 0), true_(rank_mode != 0) {
+    // (rank mode 1 keeps one slot per useful piece and none for the others: k slots, never more)
+    cap_ = fixed_ ? fixed_slots : std::max<size_t>(k, 1) + (true_ ? 0 : 1);
     m_.assign((k_ + 1) * stride(), 0);
     live_.assign(cap_, 0);
 }
@@ -242,6 +244,7 @@ void Elimination::rref() {
 }
 
 int Elimination::push(const uint8_t *coeffs, int *slot, bool *keep) {
+    if (true_) return push_true(coeffs, slot, keep);
     if (rows_ == k_) return RLNC_ERR_RECEIVED_ALL_PIECES;  // decoder.rs:97-99
     size_t s;
     if (fixed_) {
@@ -279,10 +282,62 @@ int Elimination::push(const uint8_t *coeffs, int *slot, bool *keep) {
 }
 
 void Elimination::transform(uint8_t *T, size_t ld) const {
+    if (true_) {  // rank mode 1: rows in pivot order
+        for (size_t r = 0; r < rows_; ++r) {
+            std::memcpy(T + r * ld, row(r) + k_, cap_);
+            if (ld > cap_) std::memset(T + r * ld + cap_, 0, ld - cap_);
+        }
+        return;
+    }
     for (size_t r = 0; r < rows_; ++r) {
         std::memcpy(T + r * ld, &m_[r * stride() + k_], cap_);
         if (ld > cap_) std::memset(T + r * ld + cap_, 0, ld - cap_);
     }
+}
+
+// Rank mode 1 (include/rlnc_hip.h, "Rank mode").  Rows [c | e] are stored in arrival order; the coefficient parts
+// are in reduced row-echelon form (pivot entries 1, every pivot column zero in all the other rows).  Row rows_ of the
+// (k + 1)-row matrix is the scratch for the incoming piece.
+int Elimination::push_true(const uint8_t *coeffs, int *slot, bool *keep) {
+    if (rows_ == k_) return RLNC_ERR_RECEIVED_ALL_PIECES;  // step 1: no state change
+    size_t s;
+    if (fixed_) {
+        if (pushed_ >= cap_) grow(std::max<size_t>(cap_ * 2, 1));
+        s = pushed_;
+    } else {
+        // a useful piece's slot stays live for ever (E restricted to the useful pieces is invertible), so the live
+        // slots are 0..rows_-1 and the next one is rows_ < k <= cap_
+        s = rows_;
+    }
+    ++pushed_;
+    const size_t n = stride();
+    const HostField &f = host_field();
+    uint8_t *v = &m_[rows_ * n];
+    // step 2: v = [h | unit(s)] reduced by every stored row; the quotient is the byte of h itself (RREF invariant)
+    std::memcpy(v, coeffs, k_);
+    std::memset(v + k_, 0, cap_);
+    v[k_ + s] = 1;
+    for (size_t i = 0; i < rows_; ++i) row_muladd(rows_, i, 0, coeffs[pivot_[i]]);
+    // step 3: dependent on the stored rows -- nothing is kept (the scratch row reads as zero again)
+    size_t pc = 0;
+    while (pc < k_ && v[pc] == 0) ++pc;
+    *slot = int(s);
+    if (pc == k_) {
+        std::memset(v, 0, n);
+        *keep = false;
+        return RLNC_ERR_PIECE_NOT_USEFUL;
+    }
+    // step 4: normalise v, clear column pc in the stored rows, store v with pivot pc
+    if (v[pc] != 1) gf_muladd(v, nullptr, n, f.inv[v[pc]]);
+    for (size_t i = 0; i < rows_; ++i) row_muladd(i, rows_, 0, m_[i * n + pc]);
+    size_t at = 0;
+    while (at < rows_ && pivot_[order_[at]] < pc) ++at;
+    order_.insert(order_.begin() + long(at), rows_);
+    pivot_.push_back(pc);
+    live_[s] = 1;
+    ++rows_;
+    *keep = true;
+    return RLNC_OK;
 }
 
 }  // namespace rlnc

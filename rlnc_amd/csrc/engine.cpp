@@ -76,6 +76,7 @@ struct rlnc_decoder {
     rlnc_context *ctx = nullptr;
     size_t k = 0, L = 0, stride = 0;
     size_t received = 0, useful = 0;
+    int rank_mode = 0;  // the context's rank mode when the decoder was created
     std::unique_ptr<Elimination> elim;
     uint8_t *store = nullptr;  // slot rows × stride (received data rows still referenced by E)
     size_t store_slots = 0, store_cap = 0;
@@ -488,6 +489,14 @@ int rlnc_set_decode_path(rlnc_context *ctx, int path) {
     return RLNC_OK;
 }
 
+int rlnc_set_rank_mode(rlnc_context *ctx, int mode) {
+    CHECK_ARG(ctx != nullptr && (mode == RLNC_RANK_MODE_REFERENCE || mode == RLNC_RANK_MODE_TRUE));
+    ctx->rank_mode = mode;
+    return RLNC_OK;
+}
+
+int rlnc_get_rank_mode(const rlnc_context *ctx) { return ctx ? ctx->rank_mode : -1; }
+
 int rlnc_set_kernel_variant(rlnc_context *ctx, int variant, int max_tile_rows) {
     CHECK_ARG(ctx != nullptr);
     // shipped: 0 perm, 1 nibble (the reference's tables, ablation), 6 (the unshared bit-sliced program, which also
@@ -880,7 +889,8 @@ int rlnc_decoder_new(rlnc_context *ctx, size_t L, size_t k, rlnc_decoder **out) 
     d->k = k;
     d->L = L;
     d->stride = round16(L);
-    d->elim.reset(new (std::nothrow) Elimination(k));
+    d->rank_mode = ctx->rank_mode;
+    d->elim.reset(new (std::nothrow) Elimination(k, 0, d->rank_mode));
     if (!d->elim) return set_error(RLNC_ERR_OUT_OF_MEMORY, "decoder allocation");
     *out = d.release();
     return RLNC_OK;
@@ -900,6 +910,7 @@ int rlnc_decoder_clone(const rlnc_decoder *d, rlnc_decoder **out) {
     c->stride = d->stride;
     c->received = d->received;
     c->useful = d->useful;
+    c->rank_mode = d->rank_mode;
     c->elim.reset(new (std::nothrow) Elimination(*d->elim));
     if (!c->elim) return set_error(RLNC_ERR_OUT_OF_MEMORY, "decoder allocation");
     if (d->store_slots) {
@@ -915,6 +926,8 @@ int rlnc_decoder_clone(const rlnc_decoder *d, rlnc_decoder **out) {
 }
 
 void rlnc_decoder_free(rlnc_decoder *d) { delete d; }
+
+int rlnc_decoder_get_rank_mode(const rlnc_decoder *d) { return d ? d->rank_mode : -1; }
 
 // s: the stream of the row copy (host pieces: the context's upload stream, where a store reallocation then also runs)
 static int decoder_store_slot(rlnc_decoder *d, hipStream_t s, int slot, const uint8_t *src, hipMemcpyKind kind) {
@@ -1423,6 +1436,12 @@ static int decode_eliminate_impl(rlnc_context *ctx, const uint8_t *pieces, size_
     rp.T_obj = int64_t(k * m);
     rp.status = pstat_dev;
     rp.rank = rank_dev;
+    if (ctx->rank_mode == RLNC_RANK_MODE_TRUE) {  // the true-rank producer (rank.hip): no stream, no tail
+        if (bsj_written) *bsj_written = false;
+        if (int st = ctx->rank_mode_path_check()) return st;
+        HIP_TRY(rlnc::launch_rank_batch(rp, ctx->stream));
+        return RLNC_OK;
+    }
     rp.lds_only = ctx->decode_path == 3 ? 1 : ctx->decode_path == 4 ? 2 : ctx->decode_path == 5 ? 3 : ctx->decode_path == 6 ? 4 : 0;
     if (ctx->decode_path == 5 && !rlnc::rref_block_eligible(int(k), int(m)))  // no silent fallback to another kernel
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "decode path 5 (blocked run) needs k + m <= 256 (k=%zu, m=%zu)", k, m);
@@ -1556,7 +1575,7 @@ static int decode_batch_host_impl(rlnc_context *ctx, const uint8_t *pieces, size
     std::vector<int32_t> pst(nobj * m, 0);
     auto work = [&](size_t o0, size_t o1) {
         for (size_t o = o0; o < o1; ++o) {
-            Elimination e(k, m);
+            Elimination e(k, m, ctx->rank_mode);
             for (size_t p = 0; p < m; ++p) {
                 int slot;
                 bool keep;
@@ -1638,7 +1657,7 @@ int rlnc_decode_batch(rlnc_context *ctx, const uint8_t *pieces, size_t obj_strid
     if (nobj == 0 && ctx) return RLNC_OK;
     int st = decode_batch_check(ctx, pieces, obj_stride, k, L, m, nobj, decoded);
     if (st) return st;
-    const bool fits = rlnc::rref_lds_bytes(int(k), int(m)) <= rlnc::kRrefMaxLds;
+    const bool fits = ctx->elim_fits(k, m);
     if (ctx->decode_path >= 2 && !fits)
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "device elimination forced but k=%zu, m=%zu exceed LDS", k, m);
     if (!fits || ctx->decode_path == 1)
@@ -1672,7 +1691,7 @@ int rlnc_decode_batch_device(rlnc_context *ctx, const uint8_t *pieces, size_t ob
     int st = decode_batch_check(ctx, pieces, obj_stride, k, L, m, nobj, decoded);
     if (st) return st;
     CHECK_ARG(piece_status_dev && object_status_dev && data_len_dev);
-    if (rlnc::rref_lds_bytes(int(k), int(m)) > rlnc::kRrefMaxLds)
+    if (!ctx->elim_fits(k, m))
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "k=%zu, m=%zu exceed the device elimination's LDS budget; use "
                          "rlnc_decode_batch", k, m);
     if ((st = ctx->grow(ctx->ws_rank, nobj * 4))) return st;
@@ -1687,7 +1706,7 @@ int rlnc_decode_batch_eliminate(rlnc_context *ctx, const uint8_t *pieces, size_t
     int st = decode_batch_check(ctx, pieces, obj_stride, k, L, m, nobj, T_dev);
     if (st) return st;
     CHECK_ARG(piece_status_dev && rank_dev);
-    if (rlnc::rref_lds_bytes(int(k), int(m)) > rlnc::kRrefMaxLds)
+    if (!ctx->elim_fits(k, m))
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "k=%zu, m=%zu exceed the device elimination's LDS budget; use "
                          "rlnc_decode_batch", k, m);
     return decode_eliminate_impl(ctx, pieces, obj_stride, k, L, m, nobj, T_dev, piece_status_dev, rank_dev);
@@ -1753,7 +1772,7 @@ int rlnc_decode_batch_apply_planned(rlnc_context *ctx, const uint8_t *pieces, si
 // ------------------------------------------------------------------------------------------------------
 struct rlnc_elimination {
     Elimination e;
-    explicit rlnc_elimination(size_t k, size_t fixed) : e(k, fixed) {}
+    explicit rlnc_elimination(size_t k, size_t fixed, int mode = 0) : e(k, fixed, mode) {}
 };
 
 int rlnc_elimination_new(size_t k, size_t fixed_slots, rlnc_elimination **out) {
@@ -1761,6 +1780,14 @@ int rlnc_elimination_new(size_t k, size_t fixed_slots, rlnc_elimination **out) {
     *out = nullptr;
     if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
     *out = new (std::nothrow) rlnc_elimination(k, fixed_slots);
+    return *out ? RLNC_OK : set_error(RLNC_ERR_OUT_OF_MEMORY, "elimination allocation");
+}
+int rlnc_elimination_new_mode(size_t k, size_t fixed_slots, int rank_mode, rlnc_elimination **out) {
+    CHECK_ARG(out != nullptr);
+    *out = nullptr;
+    CHECK_ARG(rank_mode == RLNC_RANK_MODE_REFERENCE || rank_mode == RLNC_RANK_MODE_TRUE);
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    *out = new (std::nothrow) rlnc_elimination(k, fixed_slots, rank_mode);
     return *out ? RLNC_OK : set_error(RLNC_ERR_OUT_OF_MEMORY, "elimination allocation");
 }
 void rlnc_elimination_free(rlnc_elimination *e) { delete e; }

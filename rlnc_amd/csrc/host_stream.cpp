@@ -249,7 +249,7 @@ int rlnc_decode_host_stream(rlnc_context *ctx, const uint8_t *pieces, size_t obj
     const size_t full = k + L, in_b = m * full, out_b = k * L;
     if (obj_stride == 0) obj_stride = in_b;
     CHECK_ARG(obj_stride >= in_b);
-    const bool dev_elim = rlnc::rref_lds_bytes(int(k), int(m)) <= rlnc::kRrefMaxLds && ctx->decode_path != 1;
+    const bool dev_elim = ctx->elim_fits(k, m) && ctx->decode_path != 1;
     int st = ctx->activate();
     if (st) return st;
     const int kin = host_kind(pieces, (nobj - 1) * obj_stride + in_b), kout = host_kind(decoded, nobj * out_b);

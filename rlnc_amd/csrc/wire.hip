@@ -429,11 +429,15 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
     }
     int st = ctx->activate();
     if (st || (st = ctx->note_capture())) return st;
+    const bool true_rank = ctx->rank_mode == RLNC_RANK_MODE_TRUE;
+    if ((st = ctx->rank_mode_path_check())) return st;
     if ((st = ctx->grow(ctx->ws_coef, tot_T)) || (st = ctx->grow(ctx->ws_rank, count * 4))) return st;
     uint8_t *T = ctx->ws_coef.as<uint8_t>();
     int32_t *rank = ctx->ws_rank.as<int32_t>();
     // 1. the exact elimination
     std::vector<rlnc::RrefObj> blk, wide;
+    std::vector<rlnc::RrefObj> tr;  // rank mode 1: the objects of the true-rank kernel (rank.hip), one launch
+    size_t lds_tr = 0;
     std::vector<size_t> host, toff(count), soff(count);
     size_t lds_blk = 0;
     int hdr_lds = 1;
@@ -446,7 +450,14 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
             toff[i] = to;
             soff[i] = so;
             rlnc::RrefObj r{o.pieces, int64_t(ps), T + to, piece_status_dev + so, rank + i, k, m, 0, 0};
-            if (rlnc::rref_block_eligible(k, m)) {
+            if (true_rank) {
+                if (ctx->elim_fits(o.k, o.m)) {
+                    tr.push_back(r);
+                    lds_tr = std::max(lds_tr, rlnc::rank_lds_bytes(k, m));
+                } else {
+                    host.push_back(i);
+                }
+            } else if (rlnc::rref_block_eligible(k, m)) {
                 blk.push_back(r);
                 lds_blk = std::max(lds_blk, rlnc::rref_block_lds_bytes_public(k, m));
             } else if (rlnc::rref_lds_bytes(k, m) <= rlnc::kRrefMaxLds) {
@@ -470,6 +481,11 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
     size_t lds_wide = 0;  // one wide object's headers not fitting beside its matrix: none are staged
     for (const auto &r : wide)
         lds_wide = std::max(lds_wide, hdr_lds ? rlnc::rref_lds_bytes_staged_public(r.k, r.m) : rlnc::rref_lds_bytes(r.k, r.m));
+    if (!tr.empty()) {
+        void *dt = nullptr;
+        if ((st = upload_table(ctx, tr.data(), tr.size() * sizeof(rlnc::RrefObj), &dt))) return st;
+        HIP_TRY(rlnc::launch_rank_ragged(static_cast<const rlnc::RrefObj *>(dt), int(tr.size()), lds_tr, ctx->stream));
+    }
     if (!blk.empty() || !wide.empty()) {
         std::vector<rlnc::RrefObj> tab(blk);
         tab.insert(tab.end(), wide.begin(), wide.end());
@@ -491,7 +507,7 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
             std::vector<int32_t> pst(o.m);
             HIP_TRY(hipMemcpy2DAsync(hdr.data(), o.k, o.pieces, ps, o.k, o.m, hipMemcpyDeviceToHost, ctx->stream));
             HIP_TRY(hipStreamSynchronize(ctx->stream));
-            rlnc::Elimination e(o.k, o.m);
+            rlnc::Elimination e(o.k, o.m, ctx->rank_mode);
             for (size_t p = 0; p < o.m; ++p) {
                 int slot;
                 bool keep;

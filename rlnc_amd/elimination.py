@@ -10,10 +10,12 @@ from .errors import check
 
 
 class Elimination:
-    def __init__(self, k: int, fixed_slots: int = 0):
+    def __init__(self, k: int, fixed_slots: int = 0, rank_mode: int = 0):
+        """rank_mode 0: the reference's diagonal-pivot replica; 1: true rank (RREF with free pivot columns; a piece
+        that is not useful keeps no slot, coefficients() returns the RREF rows in pivot order)."""
         self.lib = _lib.load()
         h = C.c_void_p()
-        check(self.lib.rlnc_elimination_new(int(k), int(fixed_slots), C.byref(h)), self.lib)
+        check(self.lib.rlnc_elimination_new_mode(int(k), int(fixed_slots), int(rank_mode), C.byref(h)), self.lib)
         self.h = h
         self.k = int(k)
 

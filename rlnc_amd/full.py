@@ -224,6 +224,11 @@ class Decoder:
 
     __copy__ = clone
 
+    @property
+    def rank_mode(self) -> int:
+        """The context's rank mode when this decoder was created (Context.set_rank_mode); clones keep it."""
+        return int(self._lib.rlnc_decoder_get_rank_mode(self._h))
+
     def decode(self, full_coded_piece) -> None:
         """Decoder::decode — decoder.rs:96-118."""
         p = _u8(full_coded_piece)

@@ -27,6 +27,9 @@ pub const RLNC_ERR_INVALID_ARGUMENT: c_int = 100;
 pub const RLNC_ERR_DEVICE: c_int = 101;
 pub const RLNC_ERR_OUT_OF_MEMORY: c_int = 102;
 pub const RLNC_ERR_NO_DEVICE: c_int = 103;
+// rank modes (rlnc_set_rank_mode)
+pub const RLNC_RANK_MODE_REFERENCE: c_int = 0;
+pub const RLNC_RANK_MODE_TRUE: c_int = 1;
 
 // ---- opaque handles ----
 #[repr(C)]
@@ -156,6 +159,8 @@ unsafe extern "C" {
     pub fn rlnc_set_kernel_variant(ctx: *mut rlnc_context, variant: c_int, max_tile_rows: c_int) -> c_int;
     pub fn rlnc_set_column_run(ctx: *mut rlnc_context, col_run: c_int) -> c_int;
     pub fn rlnc_set_decode_path(ctx: *mut rlnc_context, path: c_int) -> c_int;
+    pub fn rlnc_set_rank_mode(ctx: *mut rlnc_context, mode: c_int) -> c_int;
+    pub fn rlnc_get_rank_mode(ctx: *const rlnc_context) -> c_int;
 
     // Encoder: encoder.rs:18 (Clone), :27-39, :50-71, :85-106, :128-144, :241-250
     pub fn rlnc_encoder_new(
@@ -244,6 +249,7 @@ unsafe extern "C" {
         out: *mut *mut rlnc_decoder,
     ) -> c_int;
     pub fn rlnc_decoder_clone(dec: *const rlnc_decoder, out: *mut *mut rlnc_decoder) -> c_int;
+    pub fn rlnc_decoder_get_rank_mode(dec: *const rlnc_decoder) -> c_int;
     pub fn rlnc_decoder_free(dec: *mut rlnc_decoder);
     pub fn rlnc_decoder_decode(dec: *mut rlnc_decoder, full_coded_piece: *const u8, len: usize) -> c_int;
     pub fn rlnc_decoder_decode_device(dec: *mut rlnc_decoder, piece_dev: *const u8, len: usize) -> c_int;
@@ -468,6 +474,12 @@ unsafe extern "C" {
 
     // host-only exact coefficient elimination (decoder_matrix.rs:99-244 on [coeffs | E])
     pub fn rlnc_elimination_new(k: usize, fixed_slots: usize, out: *mut *mut rlnc_elimination) -> c_int;
+    pub fn rlnc_elimination_new_mode(
+        k: usize,
+        fixed_slots: usize,
+        rank_mode: c_int,
+        out: *mut *mut rlnc_elimination,
+    ) -> c_int;
     pub fn rlnc_elimination_free(e: *mut rlnc_elimination);
     pub fn rlnc_elimination_push(e: *mut rlnc_elimination, coeffs: *const u8, slot: *mut i32, keep: *mut i32) -> c_int;
     pub fn rlnc_elimination_rank(e: *const rlnc_elimination) -> usize;

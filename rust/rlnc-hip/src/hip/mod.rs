@@ -70,6 +70,26 @@ fn ctx() -> *mut ffi::rlnc_context {
     .0
 }
 
+/// A second process-wide context in rank mode 1 (include/rlnc_hip.h, "Rank mode"), for `Decoder::new_with_rank_mode`:
+/// the shared default context keeps the reference's mode, so no call ever switches a context another thread uses.
+fn ctx_true_rank() -> *mut ffi::rlnc_context {
+    static CTX: OnceLock<Ctx> = OnceLock::new();
+    CTX.get_or_init(|| {
+        let device = std::env::var("RLNC_HIP_DEVICE").ok().and_then(|v| v.parse().ok()).unwrap_or(0);
+        let mut c = core::ptr::null_mut();
+        // SAFETY: out-pointer to a local; the mode is set before the context is shared.
+        let mut s = unsafe { ffi::rlnc_context_create(device, &mut c) };
+        if s == ffi::RLNC_OK {
+            s = unsafe { ffi::rlnc_set_rank_mode(c, ffi::RLNC_RANK_MODE_TRUE) };
+        }
+        if s != ffi::RLNC_OK {
+            engine_failure(s);
+        }
+        Ctx(c)
+    })
+    .0
+}
+
 macro_rules! handle {
     ($T:ident, $raw:ty, $clone:path, $free:path) => {
         pub struct $T {
@@ -201,6 +221,21 @@ impl Decoder {
         let mut h = core::ptr::null_mut();
         status(unsafe { ffi::rlnc_decoder_new(ctx(), piece_byte_len, required_piece_count, &mut h) })?;
         Ok(Decoder { h })
+    }
+
+    /// Not in the reference: a decoder in true-rank mode (`true_rank`), which answers PieceNotUseful exactly for
+    /// linearly dependent pieces where the crate's diagonal-pivot elimination can count them useful (sparse or
+    /// structured coding vectors).  `false` is `Decoder::new`.
+    pub fn new_with_rank_mode(piece_byte_len: usize, required_piece_count: usize, true_rank: bool) -> Result<Decoder, RLNCError> {
+        let c = if true_rank { ctx_true_rank() } else { ctx() };
+        let mut h = core::ptr::null_mut();
+        status(unsafe { ffi::rlnc_decoder_new(c, piece_byte_len, required_piece_count, &mut h) })?;
+        Ok(Decoder { h })
+    }
+
+    /// The rank mode this decoder was created in (0 reference, 1 true rank).
+    pub fn rank_mode(&self) -> i32 {
+        unsafe { ffi::rlnc_decoder_get_rank_mode(self.h) }
     }
 
     /// decoder.rs:96-118: Ok / PieceNotUseful / ReceivedAllPieces / InvalidPieceLength, answered immediately
