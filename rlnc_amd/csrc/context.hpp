@@ -1,12 +1,16 @@
-// context.hpp — librlnc_hip internals shared by engine.cpp, host_stream.cpp and wire.cpp: error reporting, the
-// grow-only device / pinned buffers, the per-call workspace pool and struct rlnc_context (include/rlnc_hip.h).
+// context.hpp — librlnc_hip internals shared by the host sources (engine.cpp, piece_call.cpp, objects.cpp, batch.cpp,
+// host_stream.cpp, host_copy.cpp) and wire.hip: error reporting, the environment reader and the phase trace, the
+// grow-only device / pinned buffers, the per-call workspace pool, struct rlnc_context (include/rlnc_hip.h), the matmul
+// parameter builder and the result readback.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <chrono>
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <memory>
 #include <mutex>
@@ -48,6 +52,41 @@ inline int set_error(int code, const char *fmt, ...) {
     } while (0)
 
 inline size_t round16(size_t v) { return (v + 15) & ~size_t(15); }
+
+// the integer value of environment variable `name`, or dflt when it is unset (callers read once, into a static)
+inline int env_int(const char *name, int dflt) {
+    const char *e = std::getenv(name);
+    return e ? std::atoi(e) : dflt;
+}
+
+inline uint64_t now_ns() {
+    return uint64_t(std::chrono::duration_cast<std::chrono::nanoseconds>(
+                        std::chrono::steady_clock::now().time_since_epoch()).count());
+}
+
+// A diagnostic switched on by environment variable `env` = 1 (read once; it selects no path): four host times per
+// call, in us, and their medians through `fmt` (the call count, then the four) on stderr at exit.
+struct PhaseTrace {
+    const bool on;
+    const char *const fmt;
+    std::mutex mu;
+    std::vector<float> v[4];
+    PhaseTrace(const char *env, const char *f) : on(env_int(env, 0) != 0), fmt(f) {}
+    void add(float a, float b, float c, float d) {
+        std::lock_guard<std::mutex> lock(mu);
+        v[0].push_back(a);
+        v[1].push_back(b);
+        v[2].push_back(c);
+        v[3].push_back(d);
+    }
+    static float med(std::vector<float> &x) {
+        std::nth_element(x.begin(), x.begin() + x.size() / 2, x.end());
+        return x[x.size() / 2];
+    }
+    ~PhaseTrace() {
+        if (on && !v[0].empty()) std::fprintf(stderr, fmt, v[0].size(), med(v[0]), med(v[1]), med(v[2]), med(v[3]));
+    }
+};
 
 // grow-only device buffer
 struct DevBuf {
@@ -113,7 +152,7 @@ struct CallWs {
     size_t pc_pcount_words = 0;  // zeroed words of pc_pcount
     uint32_t epoch = 0;
     // large copy-outs to host (Decoder::get_decoded_data): a ring of pinned chunks the DMA fills while host threads
-    // copy the previous chunks into the caller's buffer (engine.cpp copy_out)
+    // copy the previous chunks into the caller's buffer (host_copy.cpp copy_out)
     static constexpr int kOutRing = 4;
     PinBuf pin_out;
     hipEvent_t out_ev[kOutRing] = {};
@@ -506,6 +545,43 @@ struct Lease {
     CallWs *operator->() const { return ws.get(); }
     ~Lease() { ctx->unlease(std::move(ws)); }
 };
+
+// n_obj products out[i][0:width) = XOR_j coef[i][j] · in[j][0:width) (i < n_out, j < n_in): rows at in_row / out_row,
+// objects at in_obj / out_obj, each object's coefficients dense ([n_out][n_in])
+inline rlnc::MatmulParams product_params(const uint8_t *in, size_t in_obj, size_t in_row, size_t n_in, size_t width,
+                                         const uint8_t *coef, size_t n_out, uint8_t *out, size_t out_obj,
+                                         size_t out_row, size_t n_obj) {
+    rlnc::MatmulParams p{};
+    p.in = in;
+    p.in_obj = int64_t(in_obj);
+    p.in_row = int64_t(in_row);
+    p.coef = coef;
+    p.coef_obj = int64_t(n_out * n_in);
+    p.coef_row = int64_t(n_in);
+    p.out = out;
+    p.out_obj = int64_t(out_obj);
+    p.out_row = int64_t(out_row);
+    p.n_out = int(n_out);
+    p.n_in = int(n_in);
+    p.width = int64_t(width);
+    p.n_obj = int(n_obj);
+    return p;
+}
+
+// The results of nobj objects, device -> pin (nobj · (16 + 4m) bytes of pinned memory) -> the caller's arrays, any of
+// which may be null: object statuses, data lengths and, with pstat_dev, the m piece statuses of each.  Waits for s.
+inline int read_results(uint8_t *pin, hipStream_t s, size_t nobj, const void *status_dev, const void *len_dev,
+                        const void *pstat_dev, size_t m, int32_t *object_status, uint64_t *data_len,
+                        int32_t *piece_status) {
+    HIP_TRY(hipMemcpyAsync(pin, status_dev, nobj * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(pin + nobj * 8, len_dev, nobj * 8, hipMemcpyDeviceToHost, s));
+    if (pstat_dev) HIP_TRY(hipMemcpyAsync(pin + nobj * 16, pstat_dev, nobj * m * 4, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (object_status) std::memcpy(object_status, pin, nobj * 4);
+    if (data_len) std::memcpy(data_len, pin + nobj * 8, nobj * 8);
+    if (pstat_dev && piece_status) std::memcpy(piece_status, pin + nobj * 16, nobj * m * 4);
+    return RLNC_OK;
+}
 }  // namespace rlnc::eng
 
 struct rlnc_encoder;

@@ -1,14 +1,12 @@
-// host_copy.cpp — parallel host copies (host_copy.hpp).
+// host_copy.cpp — parallel host copies and the large device -> host copy-out built on them (host_copy.hpp).
 #include "host_copy.hpp"
 
-#include <algorithm>
+#include <sys/mman.h>
+
 #include <condition_variable>
-#include <cstdint>
-#include <cstdlib>
-#include <cstring>
-#include <mutex>
 #include <thread>
-#include <vector>
+
+#include "context.hpp"
 
 namespace rlnc::eng {
 namespace {
@@ -116,10 +114,8 @@ void par_touch(void *dst, size_t n, int threads) {
 }
 
 int copy_threads() {
-    static const int t = [] {
-        if (const char *e = std::getenv("RLNC_COPY_THREADS")) return std::max(1, std::atoi(e));
-        return int(std::min<unsigned>(8, std::max<unsigned>(1, std::thread::hardware_concurrency())));
-    }();
+    static const int t = std::max(
+        1, env_int("RLNC_COPY_THREADS", int(std::min<unsigned>(8, std::thread::hardware_concurrency()))));
     return t;
 }
 
@@ -130,6 +126,87 @@ void par_copy(void *dst, const void *src, size_t n, int threads) {
         return;
     }
     pool().run(static_cast<uint8_t *>(dst), static_cast<const uint8_t *>(src), n, threads);
+}
+
+namespace {
+constexpr size_t kOutChunk = size_t(4) << 20;
+constexpr size_t kOutParallelMin = size_t(8) << 20;  // below this one pageable DMA is as fast (profiles/r05_copyout*)
+
+// RLNC_COPY_TRACE=1: per-call host time of copy_out's phases
+PhaseTrace g_copy_trace("RLNC_COPY_TRACE",
+                        "{\"copy_trace\": {\"calls\": %zu, \"median_total_us\": %.1f, \"median_event_wait_us\": %.1f, "
+                        "\"median_host_copy_us\": %.1f, \"median_first_chunk_wait_us\": %.1f}}\n");
+
+// The whole 2 MiB-aligned pages inside dst[0, n) may be backed by transparent huge pages (a hint, where the host's
+// THP mode is "madvise"): a fresh buffer then faults in 2 MiB at a time instead of 4 KiB.  The advice changes the
+// flags of the caller's mapping (they outlive the buffer in its allocator's arena), so the library gives it only when
+// the caller opts in with RLNC_COPY_HUGEPAGE=1 (read once).  A caller that owns a fresh result buffer advises it
+// itself: the C++ mirror's get_decoded_data does (include/rlnc/full.hpp), which is where the 32 MB rows' huge-page
+// gain is measured.
+void advise_huge(uint8_t *dst, size_t n) {
+    static const bool on = env_int("RLNC_COPY_HUGEPAGE", 0) != 0;
+    constexpr uintptr_t kHuge = uintptr_t(2) << 20;
+    const uintptr_t a = (reinterpret_cast<uintptr_t>(dst) + kHuge - 1) & ~(kHuge - 1);
+    const uintptr_t b = (reinterpret_cast<uintptr_t>(dst) + n) & ~(kHuge - 1);
+    if (on && b > a) (void)madvise(reinterpret_cast<void *>(a), b - a, MADV_HUGEPAGE);
+}
+
+// whether dst's pages are already mapped (a heap block the caller's allocator reused, zeroed on the caller's thread):
+// mincore on its first, middle and last pages -- a fresh mapping has none of them
+bool pages_resident(const uint8_t *dst, size_t n) {
+    for (size_t off : {size_t(0), n / 2, n - 1}) {
+        unsigned char v = 0;
+        void *a = reinterpret_cast<void *>(reinterpret_cast<uintptr_t>(dst + off) & ~(kPage - 1));
+        if (mincore(a, kPage, &v) != 0 || !(v & 1)) return false;
+    }
+    return true;
+}
+}  // namespace
+
+int copy_out(CallWs *ws, uint8_t *dst, const uint8_t *src_dev, size_t n) {
+    const int threads = copy_threads();
+    if (n < kOutParallelMin || threads <= 1) {
+        HIP_TRY(hipMemcpyAsync(dst, src_dev, n, hipMemcpyDeviceToHost, ws->stream));
+        HIP_TRY(hipStreamSynchronize(ws->stream));
+        return RLNC_OK;
+    }
+    constexpr int R = CallWs::kOutRing;
+    if (int st = ws->pin_out.ensure(size_t(R) * kOutChunk)) return st;
+    for (hipEvent_t &e : ws->out_ev)
+        if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    uint8_t *stage = ws->pin_out.as<uint8_t>();
+    advise_huge(dst, n);
+    const size_t chunks = (n + kOutChunk - 1) / kOutChunk;
+    auto issue = [&](size_t c) -> int {
+        const size_t off = c * kOutChunk, len = std::min(kOutChunk, n - off);
+        HIP_TRY(hipMemcpyAsync(stage + (c % R) * kOutChunk, src_dev + off, len, hipMemcpyDeviceToHost, ws->stream));
+        HIP_TRY(hipEventRecord(ws->out_ev[c % R], ws->stream));
+        return RLNC_OK;
+    };
+    for (size_t c = 0; c < std::min<size_t>(R, chunks); ++c)
+        if (int st = issue(c)) return st;
+    // while the device runs the product and the first chunks' DMAs: fault the caller's pages in, in parallel (a fresh
+    // buffer's page faults were most of the host copies' time: profiles/r05_copyout_trace*)
+    if (!pages_resident(dst, n)) par_touch(dst, n, threads);
+    const bool tr = g_copy_trace.on;
+    const uint64_t t0 = tr ? now_ns() : 0;
+    uint64_t tw = 0, tc = 0, tf = 0;
+    for (size_t c = 0; c < chunks; ++c) {
+        const uint64_t a = tr ? now_ns() : 0;
+        HIP_TRY(hipEventSynchronize(ws->out_ev[c % R]));
+        const uint64_t b = tr ? now_ns() : 0;
+        const size_t off = c * kOutChunk, len = std::min(kOutChunk, n - off);
+        par_copy(dst + off, stage + (c % R) * kOutChunk, len, threads);
+        if (tr) {
+            tw += b - a;
+            tc += now_ns() - b;
+            if (c == 0) tf = b - a;
+        }
+        if (c + R < chunks)
+            if (int st = issue(c + R)) return st;
+    }
+    if (tr) g_copy_trace.add((now_ns() - t0) / 1e3f, tw / 1e3f, tc / 1e3f, tf / 1e3f);
+    return RLNC_OK;
 }
 
 }  // namespace rlnc::eng

@@ -25,14 +25,10 @@ namespace {
 
 constexpr int kDefaultSlots = 3;  // profiles/r02_host_stream_ab.txt
 constexpr int kMaxSlots = 8;
-// pipeline slots (windows in flight); RLNC_HS_SLOTS (A/B knob, read once) overrides the default
+// pipeline slots (windows in flight); RLNC_HS_SLOTS (sizes the pipeline to the host, read once) overrides the default
 int num_slots() {
-    static const int n = [] {
-        const char *e = getenv("RLNC_HS_SLOTS");
-        const int v = e ? atoi(e) : kDefaultSlots;
-        return v >= 2 && v <= kMaxSlots ? v : kDefaultSlots;
-    }();
-    return n;
+    static const int v = env_int("RLNC_HS_SLOTS", kDefaultSlots);
+    return v >= 2 && v <= kMaxSlots ? v : kDefaultSlots;
 }
 
 // What a host-stream buffer [p, p + bytes) is: 1 = pinned over the whole range (hipHostMalloc, or hipHostRegister

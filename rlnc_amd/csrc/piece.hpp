@@ -41,18 +41,11 @@ struct PieceParams {
     // coef == nullptr: the coefficients are these bytes (n_out == 1): read from the kernel-argument segment in device
     // memory instead of across PCIe from pinned host memory (a round trip at the head of every workgroup)
     uint8_t coef_inline[kPieceInline];
-    // col_waves != 0 (split == 1 only): the waves of a workgroup split the columns instead of the sources -- wave w
-    // owns column block blockIdx.x · W + w and walks every source, no LDS reduction -- so a workgroup covers
-    // W · kPieceCols columns and a narrow call launches W times fewer workgroups (chunk_blocks still counts workgroups)
-    int col_waves;
 };
-
-// columns one workgroup covers for `waves` waves per workgroup
-inline int64_t piece_cols_per_wg(const PieceParams &p, int waves) { return int64_t(kPieceCols) * (p.col_waves ? waves : 1); }
 
 int piece_waves(int n_in);  // waves per workgroup for n_in sources
 int piece_split(int n_in, int64_t blocks);  // workgroups per (row, column block) for n_in sources over `blocks` of them
-int piece_chunks(const PieceParams &p, int waves);
+int piece_chunks(const PieceParams &p);
 hipError_t launch_piece(const PieceParams &p, int waves, hipStream_t s);
 // dst row j = src row j (j < n) over width bytes on the call kernel's column-block grid (src may be pinned host memory)
 hipError_t launch_piece_upload(const uint8_t *src, int64_t src_row, uint8_t *dst, int64_t dst_row, int64_t width, int n,

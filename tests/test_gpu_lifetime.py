@@ -1,4 +1,4 @@
-"""GPU: object lifetimes on a shared context (engine.cpp / context.hpp ObjUse).  Dropping an Encoder / Recoder /
+"""GPU: object lifetimes on a shared context (objects.cpp / context.hpp ObjUse).  Dropping an Encoder / Recoder /
 Decoder waits for that object's own stream-ordered uses only -- never for unrelated work queued on the context's
 stream -- and a dropped object's device block is reused by the next object only after every launch that read it,
 whichever stream the context used then."""

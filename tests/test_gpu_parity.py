@@ -820,7 +820,7 @@ def test_decode_many_small_objects(ctx, k, m, sparsity, dep, nobj):
                                                     (8, 12, 0.7, 0.1, 2049, 8192)])
 def test_decode_many_small_objects_block_products(ctx, k, m, sparsity, dep, nobj, L):
     """As above with whole 4 KiB column blocks: the T x data product takes the 1- / 2-wave bit-sliced program, whose
-    block-offset stream the small-object elimination writes itself (engine.cpp decode_batch_device_impl, RrefParams::
+    block-offset stream the small-object elimination writes itself (batch.cpp decode_batch_device_impl, RrefParams::
     bsj_stream) -- rank-deficient and dependent objects included, a ragged tail after the blocks in one case."""
     from rlnc_amd import batch
 
