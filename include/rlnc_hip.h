@@ -48,6 +48,25 @@
  *     coefficients the two modes answer alike.  The device kernel of mode 1 applies when
  *     8192 + 4·(k·D + 2·D + m·ceil(k/4) + m + 2·k + ceil(k/4)) <= 160 KiB with D = ceil(k/4) + ceil(m/4);
  *     beyond that each call does what it does in mode 0 beyond LDS (host elimination, or the same error).
+ *   - Sparse coding vectors.  The *_sparse calls take a coefficient matrix as two arrays with a fixed number w of
+ *     entries per output row: idx int32 [obj][n_out][w], the source-row index of each entry, and val uint8
+ *     [obj][n_out][w], its coefficient.  The dense row c they stand for is c[j] = XOR of val[t] over all t with
+ *     idx[t] == j.  An entry with val == 0 contributes nothing: it is padding.  An entry whose index is not in
+ *     [0, n_in) contributes nothing either, and no source row is read for it; that is a guard, not an error report
+ *     (the arrays are device-resident and cannot be validated without a synchronise).  Duplicate indices accumulate
+ *     by XOR in the header and, by linearity, in the data.  w == 0 is allowed (idx / val may then be NULL): every
+ *     output row, header included, is zero.  Every sparse call therefore writes, byte for byte, what the
+ *     corresponding dense call writes on the expanded matrix.  The coded pieces keep the crate's wire format, dense
+ *     coefficients ‖ data, so any decoder reads them (this library's in either rank mode; a sparse sender wants a
+ *     rank-mode-1 receiver).  The sparse calls always run the sparse kernel (rlnc_amd/csrc/sparse.hip: w source rows
+ *     gathered per output row, no workspace), never the dense engine; they are asynchronous on the context's stream,
+ *     never synchronise and can be captured into a HIP graph.  When to prefer the dense call on the expanded matrix
+ *     (measured on one MI355X, profiles/r08_sparse_product.jsonl, dense time / sparse time on the same input):
+ *     k = 1,024 (rows of 32 KiB): sparse 11.0x, 8.0x, 4.9x faster at w = 4, 8, 16, and by its slope (0.0102 ms per
+ *     entry against the dense call's flat 1.08 ms) up to w of about 100, a density of 1/10; k = 128 (256 KiB rows):
+ *     2.2x, 1.8x, 1.2x faster at w = 2, 4, 8 and 0.76x at w = 16 -- prefer the dense call above a density of about
+ *     1/12; k = 32 and k = 16: the dense call is faster at every w (0.79x at w = 2 of k = 32, 0.19x at w = k), because
+ *     the dense programs read each source row once per row tile where the gather reads it once per entry.
  */
 #ifndef RLNC_HIP_H
 #define RLNC_HIP_H
@@ -138,6 +157,25 @@ typedef struct rlnc_matmul_desc {
     int32_t n_obj;
 } rlnc_matmul_desc;
 int rlnc_gf256_matmul(rlnc_context *ctx, const rlnc_matmul_desc *desc);
+/* The same operator on a sparse coefficient matrix ("Sparse coding vectors" above):
+ * out[o][i][0:width) = XOR_t val[o][i][t] · in[o][idx[o][i][t]][0:width)   (t < w), and hdr (optional) receives the
+ * expanded dense rows hdr[o][i][0:n_in).  Strides in bytes; idx must be 4-byte aligned and its strides multiples of 4
+ * (else RLNC_ERR_INVALID_ARGUMENT).  Any byte alignment of in / out / hdr and any width. */
+typedef struct rlnc_sparse_matmul_desc {
+    const uint8_t *in;
+    int64_t in_obj_stride, in_row_stride;
+    const int32_t *idx;
+    int64_t idx_obj_stride, idx_row_stride;
+    const uint8_t *val;
+    int64_t val_obj_stride, val_row_stride;
+    uint8_t *out;
+    int64_t out_obj_stride, out_row_stride;
+    uint8_t *hdr;
+    int64_t hdr_obj_stride, hdr_row_stride;
+    int32_t n_out, n_in, w, n_obj;
+    int64_t width;
+} rlnc_sparse_matmul_desc;
+int rlnc_gf256_sparse_matmul(rlnc_context *ctx, const rlnc_sparse_matmul_desc *desc);
 /* Kernel variant of the GF(2^8) matmul (all bit-identical; the switch exists for A/B measurement):
  *   0 = perm       3-bit split tables in LDS consumed by v_perm_b32
  *   1 = nibble     the reference's 4-bit LOW/HIGH tables looked up from LDS byte-wise (ablation)
@@ -202,6 +240,10 @@ int rlnc_encoder_code_with_buf(rlnc_encoder *enc, const uint8_t *random_bytes, s
  * row stride out_row_stride >= k+L; pass 0 for k+L). */
 int rlnc_encoder_code_batch_device(rlnc_encoder *enc, const uint8_t *coeffs_dev, size_t n, uint8_t *out_dev,
                                    size_t out_row_stride);
+/* The sparse twin: idx_dev int32 [n][w], val_dev uint8 [n][w] ("Sparse coding vectors") → out_dev [n][k+L], the
+ * expanded dense coefficients ‖ data. */
+int rlnc_encoder_code_sparse_batch_device(rlnc_encoder *enc, const int32_t *idx_dev, const uint8_t *val_dev, size_t w,
+                                          size_t n, uint8_t *out_dev, size_t out_row_stride);
 
 /* ---- Recoder: src/full/recoder.rs ---------------------------------------------------------------- */
 typedef struct rlnc_recoder rlnc_recoder;
@@ -287,6 +329,16 @@ int rlnc_encode_batch_data_planned(rlnc_context *ctx, const uint8_t *src_dev, si
  * (recoder.rs:122-153; coefficient header and data are one linear combination of the full pieces). */
 int rlnc_recode_batch(rlnc_context *ctx, const uint8_t *pieces_dev, size_t k, size_t L, size_t n,
                       size_t num_objects, const uint8_t *r_dev, size_t count, uint8_t *out_dev);
+/* The sparse twins ("Sparse coding vectors"): idx int32 [obj][n][w], val uint8 [obj][n][w] → pieces [obj][n][k+L],
+ * the expanded dense header ‖ data: exactly what rlnc_encode_batch writes on the expanded coefficients.  Checks in
+ * rlnc_encode_batch's order; w above 0x7FFFFFFF or a misaligned idx: RLNC_ERR_INVALID_ARGUMENT. */
+int rlnc_encode_batch_sparse(rlnc_context *ctx, const uint8_t *src_dev, size_t k, size_t L, size_t num_objects,
+                             const int32_t *idx_dev, const uint8_t *val_dev, size_t w, size_t n, uint8_t *pieces_dev);
+/* idx over the n received pieces: idx / val [obj][count][w] → out [obj][count][k+L] (one linear map over the k+L
+ * bytes of the full pieces, as rlnc_recode_batch).  Checks in rlnc_recode_batch's order. */
+int rlnc_recode_batch_sparse(rlnc_context *ctx, const uint8_t *pieces_dev, size_t k, size_t L, size_t n,
+                             size_t num_objects, const int32_t *idx_dev, const uint8_t *val_dev, size_t w,
+                             size_t count, uint8_t *out_dev);
 /* Feeds pieces 0..m-1 of every object, in order, to a fresh Decoder (decoder.rs:96-118) and extracts the
  * data (decoder.rs:136-177).  decoded_dev [obj][k][L] receives the padded payload rows in the reference's
  * row order.  pieces_obj_stride = bytes between objects' first pieces (0 = m*(k+L), i.e. dense; a larger

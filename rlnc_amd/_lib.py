@@ -51,6 +51,17 @@ class MatmulDesc(C.Structure):
     ]
 
 
+class SparseMatmulDesc(C.Structure):
+    _fields_ = [
+        ("in_", C.c_void_p), ("in_obj_stride", C.c_int64), ("in_row_stride", C.c_int64),
+        ("idx", C.c_void_p), ("idx_obj_stride", C.c_int64), ("idx_row_stride", C.c_int64),
+        ("val", C.c_void_p), ("val_obj_stride", C.c_int64), ("val_row_stride", C.c_int64),
+        ("out", C.c_void_p), ("out_obj_stride", C.c_int64), ("out_row_stride", C.c_int64),
+        ("hdr", C.c_void_p), ("hdr_obj_stride", C.c_int64), ("hdr_row_stride", C.c_int64),
+        ("n_out", C.c_int32), ("n_in", C.c_int32), ("w", C.c_int32), ("n_obj", C.c_int32), ("width", C.c_int64),
+    ]
+
+
 _SIGS = {
     "rlnc_status_name": (C.c_char_p, [C.c_int]),
     "rlnc_status_message": (C.c_char_p, [C.c_int]),
@@ -69,6 +80,7 @@ _SIGS = {
     "rlnc_gf256_inplace_add_vectors": (C.c_int, [vp, vp, vp, C.c_size_t]),
     "rlnc_gf256_mul_vec_by_scalar_then_add_into_vec": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_uint8]),
     "rlnc_gf256_matmul": (C.c_int, [vp, C.POINTER(MatmulDesc)]),
+    "rlnc_gf256_sparse_matmul": (C.c_int, [vp, C.POINTER(SparseMatmulDesc)]),
     "rlnc_set_kernel_variant": (C.c_int, [vp, C.c_int, C.c_int]),
     "rlnc_set_column_run": (C.c_int, [vp, C.c_int]),
     "rlnc_set_decode_path": (C.c_int, [vp, C.c_int]),
@@ -85,6 +97,7 @@ _SIGS = {
     "rlnc_encoder_code_with_coding_vector": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t]),
     "rlnc_encoder_code_with_buf": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t]),
     "rlnc_encoder_code_batch_device": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t]),
+    "rlnc_encoder_code_sparse_batch_device": (C.c_int, [vp, vp, vp, C.c_size_t, C.c_size_t, vp, C.c_size_t]),
     "rlnc_recoder_new": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.POINTER(vp)]),
     "rlnc_recoder_clone": (C.c_int, [vp, C.POINTER(vp)]),
     "rlnc_recoder_free": (None, [vp]),
@@ -127,6 +140,10 @@ _SIGS = {
     "rlnc_decode_batch_apply_planned": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                   vp, vp, vp, vp, vp, vp]),
     "rlnc_recode_batch": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
+    "rlnc_encode_batch_sparse": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t,
+                                           vp]),
+    "rlnc_recode_batch_sparse": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t,
+                                           C.c_size_t, vp]),
     "rlnc_decode_batch": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, i32p,
                                     i32p, u64p]),
     "rlnc_decode_batch_device": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp,

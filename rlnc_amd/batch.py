@@ -13,7 +13,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import MatmulDesc
+from ._lib import MatmulDesc, SparseMatmulDesc
 from .context import Context, stream_context
 from .errors import check
 
@@ -259,6 +259,62 @@ def matmul(coef, inp, out, ctx: Context | None = None) -> None:
     d = MatmulDesc(inp.data_ptr(), n_in * W, W, coef.data_ptr(), n_out * n_in, n_in, out.data_ptr(), n_out * W, W,
                    None, 0, 0, n_out, n_in, W, nobj)
     check(ctx.lib.rlnc_gf256_matmul(ctx.h, C.byref(d)), ctx.lib)
+
+
+def _chk_sparse(idx, val, rows_shape):
+    """idx int32 / val uint8 [obj][rows][w], contiguous, on the device; returns w."""
+    import torch
+
+    assert idx.is_cuda and idx.dtype == torch.int32 and idx.is_contiguous(), "int32 contiguous device tensor required"
+    assert idx.dim() == 3 and tuple(idx.shape[:2]) == tuple(rows_shape), (tuple(idx.shape), rows_shape)
+    _chk(val, tuple(idx.shape))
+    return idx.shape[2]
+
+
+def _ptr_or_null(t):
+    return C.c_void_p(t.data_ptr() if t.numel() else None)
+
+
+def encode_batch_sparse(src, idx, val, out, ctx: Context | None = None) -> None:
+    """encode_batch from sparse coding vectors (rlnc_amd.sparse; include/rlnc_hip.h "Sparse coding vectors"):
+    idx int32 / val uint8 [obj][n][w] -> out[o][i] = dense header ‖ Σ_t val[o][i][t]·src[o][idx[o][i][t]]."""
+    nobj, k, L = src.shape
+    n = idx.shape[1]
+    _chk(src)
+    w = _chk_sparse(idx, val, (nobj, n))
+    _chk(out, (nobj, n, k + L))
+    ctx = _ctx_for(src, ctx)
+    check(ctx.lib.rlnc_encode_batch_sparse(ctx.h, C.c_void_p(src.data_ptr()), k, L, nobj, _ptr_or_null(idx),
+                                           _ptr_or_null(val), w, n, C.c_void_p(out.data_ptr())), ctx.lib)
+
+
+def recode_batch_sparse(pieces, idx, val, out, k: int, ctx: Context | None = None) -> None:
+    """recode_batch from sparse recoding vectors over the n received pieces: idx / val [obj][count][w] ->
+    out[o][c] = Σ_t val[o][c][t]·pieces[o][idx[o][c][t]] (coefficient header and data alike)."""
+    nobj, n, full = pieces.shape
+    count = idx.shape[1]
+    _chk(pieces)
+    w = _chk_sparse(idx, val, (nobj, count))
+    _chk(out, (nobj, count, full))
+    ctx = _ctx_for(pieces, ctx)
+    check(ctx.lib.rlnc_recode_batch_sparse(ctx.h, C.c_void_p(pieces.data_ptr()), k, full - k, n, nobj,
+                                           _ptr_or_null(idx), _ptr_or_null(val), w, count,
+                                           C.c_void_p(out.data_ptr())), ctx.lib)
+
+
+def sparse_matmul(idx, val, inp, out, ctx: Context | None = None) -> None:
+    """out[o][i] = Σ_t val[o][i][t]·inp[o][idx[o][i][t]] over GF(2^8); idx / val [obj][n_out][w], inp [obj][n_in][W],
+    out [obj][n_out][W]."""
+    nobj, n_in, W = inp.shape
+    n_out = idx.shape[1]
+    _chk(inp)
+    w = _chk_sparse(idx, val, (nobj, n_out))
+    _chk(out, (nobj, n_out, W))
+    ctx = _ctx_for(inp, ctx)
+    d = SparseMatmulDesc(inp.data_ptr(), n_in * W, W, idx.data_ptr() if w else None, n_out * w * 4, w * 4,
+                         val.data_ptr() if w else None, n_out * w, w, out.data_ptr(), n_out * W, W, None, 0, 0,
+                         n_out, n_in, w, nobj, W)
+    check(ctx.lib.rlnc_gf256_sparse_matmul(ctx.h, C.byref(d)), ctx.lib)
 
 
 def mul_vec_by_scalar(vec, scalar: int, ctx: Context | None = None) -> None:

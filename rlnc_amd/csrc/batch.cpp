@@ -390,6 +390,43 @@ int rlnc_recode_batch(rlnc_context *ctx, const uint8_t *pieces, size_t k, size_t
     return ctx->matmul(product_params(pieces, n * full, full, n, full, r, count, out, count * full, full, nobj));
 }
 
+// the sparse twins of rlnc_encode_batch and rlnc_recode_batch (sparse.hip): same checks in the same order, then the
+// entries'
+int rlnc_encode_batch_sparse(rlnc_context *ctx, const uint8_t *src, size_t k, size_t L, size_t nobj, const int32_t *idx,
+                             const uint8_t *val, size_t w, size_t n, uint8_t *pieces) {
+    CHECK_ARG(ctx != nullptr);
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    if (L == 0) return RLNC_ERR_PIECE_LENGTH_ZERO;
+    if (n == 0 || nobj == 0) return RLNC_OK;
+    CHECK_ARG(src && pieces && n <= 0x7FFFFFFF && k <= 0x7FFFFFFF && nobj <= 0x7FFFFFFF);
+    CHECK_ARG(sparse_entries_ok(idx, val, w));
+    int st = ctx->activate();
+    if (st || (st = ctx->note_capture())) return st;
+    const size_t full = k + L;
+    rlnc::SparseMatmulParams p =
+        sparse_product_params(src, k * L, L, k, L, idx, val, w, n, pieces + k, n * full, full, nobj);
+    p.hdr = pieces;
+    p.hdr_obj = int64_t(n * full);
+    p.hdr_row = int64_t(full);
+    return ctx->sparse_matmul(p);
+}
+
+int rlnc_recode_batch_sparse(rlnc_context *ctx, const uint8_t *pieces, size_t k, size_t L, size_t n, size_t nobj,
+                             const int32_t *idx, const uint8_t *val, size_t w, size_t count, uint8_t *out) {
+    CHECK_ARG(ctx != nullptr);
+    if (n == 0) return RLNC_ERR_NOT_ENOUGH_PIECES_TO_RECODE;
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    if (L == 0) return RLNC_ERR_PIECE_LENGTH_TOO_SHORT;
+    if (count == 0 || nobj == 0) return RLNC_OK;
+    CHECK_ARG(pieces && out && n <= 0x7FFFFFFF && count <= 0x7FFFFFFF && nobj <= 0x7FFFFFFF);
+    CHECK_ARG(sparse_entries_ok(idx, val, w));
+    int st = ctx->activate();
+    if (st || (st = ctx->note_capture())) return st;
+    const size_t full = k + L;
+    return ctx->sparse_matmul(
+        sparse_product_params(pieces, n * full, full, n, full, idx, val, w, count, out, count * full, full, nobj));
+}
+
 int rlnc_decode_batch(rlnc_context *ctx, const uint8_t *pieces, size_t obj_stride, size_t k, size_t L, size_t m,
                       size_t nobj, uint8_t *decoded, int32_t *piece_status, int32_t *object_status,
                       uint64_t *data_len) {

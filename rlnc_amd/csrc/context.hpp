@@ -21,6 +21,7 @@
 #include "../../include/rlnc_hip.h"
 #include "kernels.hpp"
 #include "rank_kernels.hpp"
+#include "sparse_kernels.hpp"
 
 namespace rlnc::eng {
 
@@ -524,6 +525,14 @@ struct rlnc_context {
         return launch(p, s, idx, batch);
     }
     int matmul(const rlnc::MatmulParams &p) { return matmul(p, stream, ws_idx, true); }
+    // the sparse product (sparse.hip) on the context stream; it takes no workspace
+    int sparse_matmul(const rlnc::SparseMatmulParams &p) {
+        if (rlnc::sparse_matmul_workgroups(p) > 0x7FFFFFFF)
+            return set_error(RLNC_ERR_INVALID_ARGUMENT, "sparse product of %d objects x %d rows x %lld bytes needs more "
+                             "than 2^31 - 1 workgroups", p.n_obj, p.n_out, static_cast<long long>(p.width));
+        HIP_TRY(rlnc::launch_sparse_matmul(p, stream));
+        return RLNC_OK;
+    }
     int launch(rlnc::MatmulParams p, hipStream_t s, DevBuf &idx, bool batch) {
         const rlnc::MatmulVariant v = variant;
         p.col_run = col_run;
@@ -566,6 +575,37 @@ inline rlnc::MatmulParams product_params(const uint8_t *in, size_t in_obj, size_
     p.width = int64_t(width);
     p.n_obj = int(n_obj);
     return p;
+}
+
+// the sparse form of product_params: each object's entries dense ([n_out][w] indices and values)
+inline rlnc::SparseMatmulParams sparse_product_params(const uint8_t *in, size_t in_obj, size_t in_row, size_t n_in,
+                                                      size_t width, const int32_t *idx, const uint8_t *val, size_t w,
+                                                      size_t n_out, uint8_t *out, size_t out_obj, size_t out_row,
+                                                      size_t n_obj) {
+    rlnc::SparseMatmulParams p{};
+    p.in = in;
+    p.in_obj = int64_t(in_obj);
+    p.in_row = int64_t(in_row);
+    p.idx = idx;
+    p.idx_obj = int64_t(n_out * w * 4);
+    p.idx_row = int64_t(w * 4);
+    p.val = val;
+    p.val_obj = int64_t(n_out * w);
+    p.val_row = int64_t(w);
+    p.out = out;
+    p.out_obj = int64_t(out_obj);
+    p.out_row = int64_t(out_row);
+    p.n_out = int(n_out);
+    p.n_in = int(n_in);
+    p.w = int(w);
+    p.n_obj = int(n_obj);
+    p.width = int64_t(width);
+    return p;
+}
+// idx / val of a sparse call: both present unless w == 0, idx readable as int32
+inline bool sparse_entries_ok(const int32_t *idx, const uint8_t *val, size_t w) {
+    return w <= 0x7FFFFFFF && (w == 0 || (idx != nullptr && val != nullptr)) &&
+           (reinterpret_cast<uintptr_t>(idx) & 3) == 0;
 }
 
 // The results of nobj objects, device -> pin (nobj · (16 + 4m) bytes of pinned memory) -> the caller's arrays, any of

@@ -242,6 +242,39 @@ int rlnc_gf256_matmul(rlnc_context *ctx, const rlnc_matmul_desc *desc) {
     return ctx->matmul(p);
 }
 
+int rlnc_gf256_sparse_matmul(rlnc_context *ctx, const rlnc_sparse_matmul_desc *desc) {
+    CHECK_ARG(ctx != nullptr && desc != nullptr);
+    CHECK_ARG(desc->n_out >= 0 && desc->n_in >= 0 && desc->w >= 0 && desc->width >= 0 && desc->n_obj >= 0);
+    if (desc->n_out == 0 || desc->width == 0 || desc->n_obj == 0) return RLNC_OK;
+    CHECK_ARG(desc->n_in > 0 && desc->in && desc->out && (desc->w == 0 || (desc->idx && desc->val)));
+    CHECK_ARG((reinterpret_cast<uintptr_t>(desc->idx) & 3) == 0 && (desc->idx_obj_stride & 3) == 0 &&
+              (desc->idx_row_stride & 3) == 0);
+    int st = ctx->activate();
+    if (st || (st = ctx->note_capture())) return st;
+    rlnc::SparseMatmulParams p{};
+    p.in = desc->in;
+    p.in_obj = desc->in_obj_stride;
+    p.in_row = desc->in_row_stride;
+    p.idx = desc->idx;
+    p.idx_obj = desc->idx_obj_stride;
+    p.idx_row = desc->idx_row_stride;
+    p.val = desc->val;
+    p.val_obj = desc->val_obj_stride;
+    p.val_row = desc->val_row_stride;
+    p.out = desc->out;
+    p.out_obj = desc->out_obj_stride;
+    p.out_row = desc->out_row_stride;
+    p.hdr = desc->hdr;
+    p.hdr_obj = desc->hdr_obj_stride;
+    p.hdr_row = desc->hdr_row_stride;
+    p.n_out = desc->n_out;
+    p.n_in = desc->n_in;
+    p.w = desc->w;
+    p.n_obj = desc->n_obj;
+    p.width = desc->width;
+    return ctx->sparse_matmul(p);
+}
+
 // ------------------------------------------------------------------------------------------------------
 // host-only access to the decoder's elimination engine (no device needed; CPU-testable host logic)
 // ------------------------------------------------------------------------------------------------------

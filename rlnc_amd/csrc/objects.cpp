@@ -257,6 +257,24 @@ int rlnc_encoder_code_batch_device(rlnc_encoder *e, const uint8_t *coeffs_dev, s
     return e->owned ? e->use.note(e->ctx->stream) : RLNC_OK;
 }
 
+// the same from sparse coding vectors (sparse.hip): idx / val [n][w] -> out[i] = expanded cv[i] ‖ data
+int rlnc_encoder_code_sparse_batch_device(rlnc_encoder *e, const int32_t *idx_dev, const uint8_t *val_dev, size_t w,
+                                          size_t n, uint8_t *out_dev, size_t out_row_stride) {
+    CHECK_ARG(e != nullptr);
+    if (n == 0) return RLNC_OK;
+    CHECK_ARG(out_dev != nullptr && n <= 0x7FFFFFFF && e->k <= 0x7FFFFFFF);
+    CHECK_ARG(sparse_entries_ok(idx_dev, val_dev, w));
+    const size_t row = out_row_stride ? out_row_stride : e->k + e->L;
+    CHECK_ARG(row >= e->k + e->L);
+    int st = e->ctx->activate();
+    if (st || (st = e->ctx->note_capture())) return st;
+    auto p = sparse_product_params(e->src, 0, e->stride, e->k, e->L, idx_dev, val_dev, w, n, out_dev + e->k, 0, row, 1);
+    p.hdr = out_dev;
+    p.hdr_row = int64_t(row);
+    if ((st = e->ctx->sparse_matmul(p))) return st;
+    return e->owned ? e->use.note(e->ctx->stream) : RLNC_OK;
+}
+
 // ------------------------------------------------------------------------------------------------------
 // Recoder — recoder.rs
 // ------------------------------------------------------------------------------------------------------

@@ -126,6 +126,13 @@ class Encoder:
         check(self._lib.rlnc_encoder_code_batch_device(self._h, C.c_void_p(coeffs_dev_ptr), n,
                                                        C.c_void_p(out_dev_ptr), out_row_stride), self._lib)
 
+    def code_sparse_batch_device(self, idx_ptr: int, val_ptr: int, w: int, n: int, out_ptr: int,
+                                 out_row_stride: int = 0) -> None:
+        """code_batch_device from sparse coding vectors (rlnc_amd.sparse): idx int32 [n][w], val uint8 [n][w] on the
+        device -> n coded pieces, expanded dense coefficients ‖ data."""
+        check(self._lib.rlnc_encoder_code_sparse_batch_device(self._h, C.c_void_p(idx_ptr), C.c_void_p(val_ptr), w, n,
+                                                              C.c_void_p(out_ptr), out_row_stride), self._lib)
+
 
 class Recoder:
     """rlnc::full::Recoder (recoder.rs:13-172)."""

@@ -77,6 +77,31 @@ pub struct rlnc_matmul_desc {
 
 #[repr(C)]
 #[derive(Clone, Copy, Debug)]
+pub struct rlnc_sparse_matmul_desc {
+    pub in_: *const u8,
+    pub in_obj_stride: i64,
+    pub in_row_stride: i64,
+    pub idx: *const i32,
+    pub idx_obj_stride: i64,
+    pub idx_row_stride: i64,
+    pub val: *const u8,
+    pub val_obj_stride: i64,
+    pub val_row_stride: i64,
+    pub out: *mut u8,
+    pub out_obj_stride: i64,
+    pub out_row_stride: i64,
+    pub hdr: *mut u8,
+    pub hdr_obj_stride: i64,
+    pub hdr_row_stride: i64,
+    pub n_out: i32,
+    pub n_in: i32,
+    pub w: i32,
+    pub n_obj: i32,
+    pub width: i64,
+}
+
+#[repr(C)]
+#[derive(Clone, Copy, Debug)]
 pub struct rlnc_pad_desc {
     pub data: *const u8,
     pub data_len: usize,
@@ -156,6 +181,7 @@ unsafe extern "C" {
 
     // L2 matrix operator
     pub fn rlnc_gf256_matmul(ctx: *mut rlnc_context, desc: *const rlnc_matmul_desc) -> c_int;
+    pub fn rlnc_gf256_sparse_matmul(ctx: *mut rlnc_context, desc: *const rlnc_sparse_matmul_desc) -> c_int;
     pub fn rlnc_set_kernel_variant(ctx: *mut rlnc_context, variant: c_int, max_tile_rows: c_int) -> c_int;
     pub fn rlnc_set_column_run(ctx: *mut rlnc_context, col_run: c_int) -> c_int;
     pub fn rlnc_set_decode_path(ctx: *mut rlnc_context, path: c_int) -> c_int;
@@ -207,6 +233,15 @@ unsafe extern "C" {
     pub fn rlnc_encoder_code_batch_device(
         enc: *mut rlnc_encoder,
         coeffs_dev: *const u8,
+        n: usize,
+        out_dev: *mut u8,
+        out_row_stride: usize,
+    ) -> c_int;
+    pub fn rlnc_encoder_code_sparse_batch_device(
+        enc: *mut rlnc_encoder,
+        idx_dev: *const i32,
+        val_dev: *const u8,
+        w: usize,
         n: usize,
         out_dev: *mut u8,
         out_row_stride: usize,
@@ -331,6 +366,32 @@ unsafe extern "C" {
         n: usize,
         num_objects: usize,
         r_dev: *const u8,
+        count: usize,
+        out_dev: *mut u8,
+    ) -> c_int;
+    // sparse coding vectors: idx int32 / val uint8 [obj][rows][w] instead of dense coefficients
+    pub fn rlnc_encode_batch_sparse(
+        ctx: *mut rlnc_context,
+        src_dev: *const u8,
+        k: usize,
+        L: usize,
+        num_objects: usize,
+        idx_dev: *const i32,
+        val_dev: *const u8,
+        w: usize,
+        n: usize,
+        pieces_dev: *mut u8,
+    ) -> c_int;
+    pub fn rlnc_recode_batch_sparse(
+        ctx: *mut rlnc_context,
+        pieces_dev: *const u8,
+        k: usize,
+        L: usize,
+        n: usize,
+        num_objects: usize,
+        idx_dev: *const i32,
+        val_dev: *const u8,
+        w: usize,
         count: usize,
         out_dev: *mut u8,
     ) -> c_int;
