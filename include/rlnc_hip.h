@@ -47,7 +47,10 @@
  *     independent of the useful pieces before it; at rank k, T × data is the source as in mode 0.  On dense random
  *     coefficients the two modes answer alike.  The device kernel of mode 1 applies when
  *     8192 + 4·(k·D + 2·D + m·ceil(k/4) + m + 2·k + ceil(k/4)) <= 160 KiB with D = ceil(k/4) + ceil(m/4);
- *     beyond that each call does what it does in mode 0 beyond LDS (host elimination, or the same error).
+ *     beyond that each call does what it does in mode 0 beyond LDS (host elimination, or the same error) -- unless
+ *     decode path 7 is set (rlnc_set_decode_path): then a second set of kernels keeps the same rows in a device
+ *     workspace, takes the pieces B <= 32 at a time (three launches per block, one at the end, none synchronising) and
+ *     produces the same T, statuses and rank for k <= 4096, m <= 8192.
  *   - Sparse coding vectors.  The *_sparse calls take a coefficient matrix as two arrays with a fixed number w of
  *     entries per output row: idx int32 [obj][n_out][w], the source-row index of each entry, and val uint8
  *     [obj][n_out][w], its coefficient.  The dense row c they stand for is c[j] = XOR of val[t] over all t with
@@ -198,13 +201,26 @@ int rlnc_set_column_run(rlnc_context *ctx, int col_run);
 /* Where rlnc_decode_batch runs the coefficient elimination: 0 = auto (device when it fits LDS, default),
  * 1 = host threads, 2 = device, 5 = device, blocked clean run (k + m <= 256, else RLNC_ERR_INVALID_ARGUMENT; what 0
  * and 2 use when it applies).  The A/B build adds 3 (clean state on LDS), 4 (one wave's registers) and 6 (the
- * round-1 multi-wave register path).  All are exact replicas; the switch exists for A/B tests. */
+ * round-1 multi-wave register path).  All of these are exact replicas; the switch exists for A/B tests.
+ * Rank mode 1 only (in mode 0 every decode call under them returns RLNC_ERR_INVALID_ARGUMENT, no silent fallback):
+ * RLNC_DECODE_PATH_DEVICE_ANY (7) = the device for every shape -- the LDS kernel where it fits, beyond that the
+ * workspace-resident true-rank kernels (rlnc_amd/csrc/rank_large.hip), so rlnc_decode_batch makes no host round trip
+ * for the elimination, rlnc_decode_batch_device / _eliminate accept the shape, and a ragged decode with such objects
+ * stays on the stream and can be captured; RLNC_DECODE_PATH_LARGE (8) = those kernels for every shape, small ones
+ * included (tests and A/Bs).  Their limits: k <= 4096, m <= 8192, else RLNC_ERR_INVALID_ARGUMENT. */
+#define RLNC_DECODE_PATH_DEVICE_ANY 7
+#define RLNC_DECODE_PATH_LARGE 8
 int rlnc_set_decode_path(rlnc_context *ctx, int path);
+/* Device workspace, in bytes, that decode paths 7 and 8 keep in the context for num_objects objects of k x m beyond LDS
+ * (it grows on the first eager call of a shape; under a HIP graph capture a grow is refused, see "HIP graphs").  0 for a
+ * shape outside their limits.  Pure: needs no context and no GPU. */
+size_t rlnc_decode_large_workspace_bytes(size_t k, size_t m, size_t num_objects);
 /* Rank mode of the context (see "Rank mode" above): governs rlnc_decode_batch, rlnc_decode_batch_device,
  * rlnc_decode_batch_eliminate, rlnc_decode_ragged and rlnc_decode_host_stream, and is snapshotted by rlnc_decoder_new.
  * Other values: RLNC_ERR_INVALID_ARGUMENT.  In mode 1 decode paths 0 and 2 use the true-rank device kernel when it
- * fits, path 1 the host; path 5 (and the A/B build's 3, 4, 6) name reference-mode kernels and make the decode calls
- * return RLNC_ERR_INVALID_ARGUMENT (no silent fallback). */
+ * fits, path 1 the host, paths 7 and 8 the device for every shape (rlnc_set_decode_path); path 5 (and the A/B build's
+ * 3, 4, 6) name reference-mode kernels and make the decode calls return RLNC_ERR_INVALID_ARGUMENT (no silent
+ * fallback). */
 #define RLNC_RANK_MODE_REFERENCE 0
 #define RLNC_RANK_MODE_TRUE 1
 int rlnc_set_rank_mode(rlnc_context *ctx, int mode);

@@ -62,6 +62,10 @@ class SparseMatmulDesc(C.Structure):
     ]
 
 
+# decode paths of rank mode 1 beyond LDS (include/rlnc_hip.h, rlnc_set_decode_path)
+RLNC_DECODE_PATH_DEVICE_ANY = 7
+RLNC_DECODE_PATH_LARGE = 8
+
 _SIGS = {
     "rlnc_status_name": (C.c_char_p, [C.c_int]),
     "rlnc_status_message": (C.c_char_p, [C.c_int]),
@@ -135,6 +139,7 @@ _SIGS = {
     "rlnc_decode_batch_apply": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp,
                                           vp, vp, vp, vp]),
     "rlnc_decode_batch_apply_plan_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t]),
+    "rlnc_decode_large_workspace_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t]),
     "rlnc_decode_batch_apply_prepare": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                   vp, vp, vp, C.c_size_t]),
     "rlnc_decode_batch_apply_planned": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,

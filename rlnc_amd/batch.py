@@ -214,6 +214,14 @@ def decode_apply_plan_bytes(k: int, m: int, nobj: int) -> int:
     return int(load().rlnc_decode_batch_apply_plan_bytes(k, m, nobj))
 
 
+def decode_large_workspace_bytes(k: int, m: int, nobj: int) -> int:
+    """Device bytes decode paths 7 and 8 keep in the context for nobj objects of k x m (0: outside their limits,
+    k <= 4096 and m <= 8192).  Needs no GPU."""
+    from ._lib import load
+
+    return int(load().rlnc_decode_large_workspace_bytes(k, m, nobj))
+
+
 def decode_batch_apply_prepare(pieces, k: int, T, decoded, plan, ctx: Context | None = None):
     """The code-block address stream of decode_batch_apply(pieces, k, T, ..., decoded) written ahead into `plan` (a
     uint8 device tensor of decode_apply_plan_bytes bytes) on this context's stream, once T is final -- e.g. behind

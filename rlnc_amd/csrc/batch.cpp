@@ -155,9 +155,17 @@ int decode_eliminate_impl(rlnc_context *ctx, const uint8_t *pieces, size_t obj_s
     if (ctx->rank_mode == RLNC_RANK_MODE_TRUE) {  // the true-rank producer (rank.hip): no stream, no tail
         if (bsj_written) *bsj_written = false;
         if (int st = ctx->rank_mode_path_check()) return st;
+        if (ctx->elim_large(k, m)) {  // paths 7 / 8: the state in a workspace, 3·ceil(m / B) + 1 launches (rank_large.hip)
+            if (int st = rlnc_context::large_shape_check(k, m)) return st;
+            const size_t need = rlnc::rank_large_workspace_bytes(k, m, nobj);
+            if (int st = ctx->grow(ctx->ws_large, need)) return st;
+            HIP_TRY(rlnc::launch_rank_large(rp, ctx->ws_large.p, ctx->ws_large.cap, ctx->stream));
+            return RLNC_OK;
+        }
         HIP_TRY(rlnc::launch_rank_batch(rp, ctx->stream));
         return RLNC_OK;
     }
+    if (int st = ctx->rank_mode_path_check()) return st;  // paths 7 and 8 in mode 0
     rp.lds_only = ctx->decode_path == 3 ? 1 : ctx->decode_path == 4 ? 2 : ctx->decode_path == 5 ? 3 : ctx->decode_path == 6 ? 4 : 0;
     if (ctx->decode_path == 5 && !rlnc::rref_block_eligible(int(k), int(m)))  // no silent fallback to another kernel
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "decode path 5 (blocked run) needs k + m <= 256 (k=%zu, m=%zu)", k, m);
@@ -433,7 +441,8 @@ int rlnc_decode_batch(rlnc_context *ctx, const uint8_t *pieces, size_t obj_strid
     if (nobj == 0 && ctx) return RLNC_OK;
     int st = decode_batch_check(ctx, pieces, obj_stride, k, L, m, nobj, decoded);
     if (st) return st;
-    const bool fits = ctx->elim_fits(k, m);
+    if ((st = ctx->rank_mode_path_check())) return st;
+    const bool fits = ctx->elim_on_device(k, m);
     if (ctx->decode_path >= 2 && !fits)
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "device elimination forced but k=%zu, m=%zu exceed LDS", k, m);
     if (!fits || ctx->decode_path == 1)
@@ -458,7 +467,8 @@ int rlnc_decode_batch_device(rlnc_context *ctx, const uint8_t *pieces, size_t ob
     int st = decode_batch_check(ctx, pieces, obj_stride, k, L, m, nobj, decoded);
     if (st) return st;
     CHECK_ARG(piece_status_dev && object_status_dev && data_len_dev);
-    if (!ctx->elim_fits(k, m))
+    if ((st = ctx->rank_mode_path_check())) return st;
+    if (!ctx->elim_on_device(k, m))
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "k=%zu, m=%zu exceed the device elimination's LDS budget; use "
                          "rlnc_decode_batch", k, m);
     if ((st = ctx->grow(ctx->ws_rank, nobj * 4))) return st;
@@ -473,7 +483,8 @@ int rlnc_decode_batch_eliminate(rlnc_context *ctx, const uint8_t *pieces, size_t
     int st = decode_batch_check(ctx, pieces, obj_stride, k, L, m, nobj, T_dev);
     if (st) return st;
     CHECK_ARG(piece_status_dev && rank_dev);
-    if (!ctx->elim_fits(k, m))
+    if ((st = ctx->rank_mode_path_check())) return st;
+    if (!ctx->elim_on_device(k, m))
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "k=%zu, m=%zu exceed the device elimination's LDS budget; use "
                          "rlnc_decode_batch", k, m);
     return decode_eliminate_impl(ctx, pieces, obj_stride, k, L, m, nobj, T_dev, piece_status_dev, rank_dev);
@@ -488,6 +499,10 @@ int rlnc_decode_batch_apply(rlnc_context *ctx, const uint8_t *pieces, size_t obj
     CHECK_ARG(T_dev && rank_dev && object_status_dev && data_len_dev);
     return decode_apply_impl(ctx, decode_apply_params(pieces, obj_stride, k, L, m, nobj, T_dev, decoded), k, L, nobj,
                              rank_dev, object_status_dev, data_len_dev);
+}
+
+size_t rlnc_decode_large_workspace_bytes(size_t k, size_t m, size_t nobj) {
+    return rlnc::rank_large_workspace_bytes(k, m, nobj);
 }
 
 size_t rlnc_decode_batch_apply_plan_bytes(size_t k, size_t m, size_t nobj) {

@@ -21,6 +21,7 @@
 #include "../../include/rlnc_hip.h"
 #include "kernels.hpp"
 #include "rank_kernels.hpp"
+#include "rank_large_kernels.hpp"
 #include "sparse_kernels.hpp"
 
 namespace rlnc::eng {
@@ -243,24 +244,47 @@ struct rlnc_context {
     int col_run = 0;  // column blocks per workgroup of variant 9 (0 = chosen per launch; rlnc_set_column_run)
     int decode_path = 0;  // 0 auto (device when it fits LDS), 1 host elimination, 2 device elimination,
                           // 3 device elimination with the clean state on LDS, 4 ... on one wave's
-                          // registers, 5 blocked clean run, 6 round-1 multi-wave registers (A/B)
+                          // registers, 5 blocked clean run, 6 round-1 multi-wave registers (A/B),
+                          // 7 device for every shape (rank mode 1: rank.hip where it fits LDS, rank_large.hip
+                          // beyond), 8 rank_large.hip for every shape
     int rank_mode = 0;  // RLNC_RANK_MODE_*: 0 the reference's diagonal-pivot replica, 1 true rank (rank.hip, elimination.hpp)
     // the device elimination of this context's rank mode fits LDS
     bool elim_fits(size_t k, size_t m) const {
         return (rank_mode == RLNC_RANK_MODE_TRUE ? rlnc::rank_lds_bytes(int(k), int(m)) : rlnc::rref_lds_bytes(int(k), int(m))) <=
                rlnc::kRrefMaxLds;
     }
-    // decode paths 3-6 name reference-mode kernels: no silent fallback in true-rank mode
+    // the elimination of this shape runs in the workspace-resident true-rank kernels (rank_large.hip): path 8 always,
+    // path 7 beyond LDS (rank mode 1 only: rank_mode_path_check refuses both paths in mode 0)
+    bool elim_large(size_t k, size_t m) const {
+        return decode_path == RLNC_DECODE_PATH_LARGE || (decode_path == RLNC_DECODE_PATH_DEVICE_ANY && !elim_fits(k, m));
+    }
+    // the elimination of this shape can run on the device
+    bool elim_on_device(size_t k, size_t m) const { return elim_fits(k, m) || elim_large(k, m); }
+    // decode paths 3-6 name reference-mode kernels, 7 and 8 true-rank kernels: no silent fallback in the other mode
     int rank_mode_path_check() const {
-        if (rank_mode == RLNC_RANK_MODE_TRUE && decode_path >= 3)
+        const bool large = decode_path == RLNC_DECODE_PATH_DEVICE_ANY || decode_path == RLNC_DECODE_PATH_LARGE;
+        if (rank_mode == RLNC_RANK_MODE_TRUE && decode_path >= 3 && !large)
             return set_error(RLNC_ERR_INVALID_ARGUMENT,
-                             "decode path %d is a reference-mode kernel: rank mode 1 takes paths 0, 1 and 2", decode_path);
+                             "decode path %d is a reference-mode kernel: rank mode 1 takes paths 0, 1, 2, 7 and 8",
+                             decode_path);
+        if (rank_mode != RLNC_RANK_MODE_TRUE && large)
+            return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                             "decode path %d is a true-rank kernel: rank mode 0 takes paths 0, 1, 2 and 5", decode_path);
+        return RLNC_OK;
+    }
+    // the shape limits of rank_large.hip, by name
+    static int large_shape_check(size_t k, size_t m) {
+        if (rlnc::large_block(int64_t(std::min<size_t>(k, 0x7FFFFFFF)), int64_t(std::min<size_t>(m, 0x7FFFFFFF))) == 0)
+            return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                             "decode paths 7 and 8 take k <= %d and m <= %d beyond LDS (k=%zu, m=%zu)", rlnc::kLargeMaxK,
+                             rlnc::kLargeMaxM, k, m);
         return RLNC_OK;
     }
     // workspaces of the stream-ordered batch / _device API (one caller thread per context at a time)
     DevBuf ws_bsj;   // the small-object decode's block-offset stream, written by its elimination
     DevBuf ws_need;  // ... and its per-object "payload tail all zero" flags (RrefParams::tail_need)
     DevBuf ws_coef, ws_out, ws_status, ws_len, ws_pstat, ws_rank, ws_idx;
+    DevBuf ws_large;  // the state of the workspace-resident true-rank elimination (rank_large.hip)
     PinBuf pin_a, pin_b, pin_c;
     // set once a batch call ran inside a HIP stream capture: the graph holds the workspace addresses, so
     // they must never move again (grow() refuses instead of reallocating)

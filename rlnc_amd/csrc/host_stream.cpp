@@ -245,9 +245,9 @@ int rlnc_decode_host_stream(rlnc_context *ctx, const uint8_t *pieces, size_t obj
     const size_t full = k + L, in_b = m * full, out_b = k * L;
     if (obj_stride == 0) obj_stride = in_b;
     CHECK_ARG(obj_stride >= in_b);
-    const bool dev_elim = ctx->elim_fits(k, m) && ctx->decode_path != 1;
+    const bool dev_elim = ctx->elim_on_device(k, m) && ctx->decode_path != 1;
     int st = ctx->activate();
-    if (st) return st;
+    if (st || (st = ctx->rank_mode_path_check())) return st;
     const int kin = host_kind(pieces, (nobj - 1) * obj_stride + in_b), kout = host_kind(decoded, nobj * out_b);
     if (kin < 0 || kout < 0)
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "host-stream buffers must be host memory (got a device pointer)");

@@ -412,7 +412,8 @@ int rlnc_recode_ragged(rlnc_context *ctx, const rlnc_recode_object_desc *objs, s
 
 // Decoder::decode over pieces 0..m-1 + get_decoded_data (decoder.rs:96-177) for every object: the exact elimination
 // (one launch for the objects whose [coeffs | E] fits a wave's row, k + m <= 256, one for larger ones that fit LDS;
-// host threads for any beyond LDS), T × received data (the ragged matmul, <= 4 launches), the marker scan (1 launch)
+// host threads for any beyond LDS -- or, in rank mode 1 under decode paths 7 / 8, rank_large.hip's launches on the
+// stream), T × received data (the ragged matmul, <= 4 launches), the marker scan (1 launch)
 int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, size_t count, int32_t *piece_status_dev,
                        int32_t *object_status_dev, int64_t *data_len_dev) {
     CHECK_ARG(ctx != nullptr);
@@ -438,7 +439,8 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
     std::vector<rlnc::RrefObj> blk, wide;
     std::vector<rlnc::RrefObj> tr;  // rank mode 1: the objects of the true-rank kernel (rank.hip), one launch
     size_t lds_tr = 0;
-    std::vector<size_t> host, toff(count), soff(count);
+    std::vector<size_t> host, large, toff(count), soff(count);
+    size_t large_ws = 0;
     size_t lds_blk = 0;
     int hdr_lds = 1;
     {
@@ -451,7 +453,11 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
             soff[i] = so;
             rlnc::RrefObj r{o.pieces, int64_t(ps), T + to, piece_status_dev + so, rank + i, k, m, 0, 0};
             if (true_rank) {
-                if (ctx->elim_fits(o.k, o.m)) {
+                if (ctx->elim_large(o.k, o.m)) {  // paths 7 / 8: a one-object batch of rank_large.hip, on the stream
+                    if ((st = rlnc_context::large_shape_check(o.k, o.m))) return st;
+                    large.push_back(i);
+                    large_ws = std::max(large_ws, rlnc::rank_large_workspace_bytes(o.k, o.m, 1));
+                } else if (ctx->elim_fits(o.k, o.m)) {
                     tr.push_back(r);
                     lds_tr = std::max(lds_tr, rlnc::rank_lds_bytes(k, m));
                 } else {
@@ -494,6 +500,22 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
         const auto *t = static_cast<const rlnc::RrefObj *>(dt);
         HIP_TRY(rlnc::launch_rref_ragged(t, int(blk.size()), true, lds_blk, 1, ctx->stream));
         HIP_TRY(rlnc::launch_rref_ragged(t + blk.size(), int(wide.size()), false, lds_wide, hdr_lds, ctx->stream));
+    }
+    if (!large.empty()) {  // one after another in the one workspace: the stream orders them
+        if ((st = ctx->grow(ctx->ws_large, large_ws))) return st;
+        for (size_t i : large) {
+            const rlnc_decode_object_desc &o = objs[i];
+            rlnc::RrefParams rp{};
+            rp.pieces = o.pieces;
+            rp.piece_stride = int64_t(o.piece_row_stride ? o.piece_row_stride : o.k + o.L);
+            rp.k = int(o.k);
+            rp.m = int(o.m);
+            rp.n_obj = 1;
+            rp.T = T + toff[i];
+            rp.status = piece_status_dev + soff[i];
+            rp.rank = rank + i;
+            HIP_TRY(rlnc::launch_rank_large(rp, ctx->ws_large.p, ctx->ws_large.cap, ctx->stream));
+        }
     }
     if (!host.empty()) {  // beyond LDS (k of several hundred): host threads' exact elimination, T and statuses uploaded
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;

@@ -30,6 +30,9 @@ pub const RLNC_ERR_NO_DEVICE: c_int = 103;
 // rank modes (rlnc_set_rank_mode)
 pub const RLNC_RANK_MODE_REFERENCE: c_int = 0;
 pub const RLNC_RANK_MODE_TRUE: c_int = 1;
+// decode paths of rank mode 1 for every shape (rlnc_set_decode_path)
+pub const RLNC_DECODE_PATH_DEVICE_ANY: c_int = 7;
+pub const RLNC_DECODE_PATH_LARGE: c_int = 8;
 
 // ---- opaque handles ----
 #[repr(C)]
@@ -448,6 +451,7 @@ unsafe extern "C" {
         data_len_dev: *mut i64,
     ) -> c_int;
     pub fn rlnc_decode_batch_apply_plan_bytes(k: usize, m: usize, num_objects: usize) -> usize;
+    pub fn rlnc_decode_large_workspace_bytes(k: usize, m: usize, num_objects: usize) -> usize;
     pub fn rlnc_decode_batch_apply_prepare(
         ctx: *mut rlnc_context,
         pieces_dev: *const u8,

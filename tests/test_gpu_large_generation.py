@@ -1,0 +1,400 @@
+"""GPU: the true-rank elimination for generations beyond LDS (rlnc_amd/csrc/rank_large.hip) -- decode path 8 (those
+kernels for every shape) at the smallest shapes at which they can go wrong, and decode path 7 (the device for every
+shape) through decode_batch_eliminate / decode_batch_device / decode_batch / decode_ragged / decode_host_stream --
+against the numpy model of tests/test_true_rank_host.py.  All comparisons are exact."""
+import contextlib
+import ctypes as C
+import functools
+
+import numpy as np
+import pytest
+
+from oracle import np_oracle as npo
+from tests.gpu_util import dev, host, np_matmul
+from tests.test_true_rank_host import FIXTURE, NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
+
+pytestmark = pytest.mark.gpu
+NOT_ALL_YET = 10
+DEVICE_ANY, LARGE = 7, 8
+MUL = npo.mul_table()
+
+
+def block_pieces(k, m):
+    """Pieces per block of rank_large.hip (rank_large_kernels.hpp, large_block): the largest multiple of 4, at most
+    32, whose rows fit the block step's LDS beside 8 KiB + 1 KiB."""
+    D = (k + 3) // 4 + (m + 3) // 4
+    return min(32, (160 * 1024 - 8192 - 1024) // (4 * D)) & ~3
+
+
+@pytest.fixture(scope="module")
+def ctx1():
+    """A context in rank mode 1 (tests set its decode path through `path` and get path 0 back)."""
+    import torch
+
+    assert torch.cuda.is_available(), "GPU tests need the MI355X"
+    import rlnc_amd
+
+    c = rlnc_amd.Context(0)
+    c.set_rank_mode(1)
+    return c
+
+
+@contextlib.contextmanager
+def path(ctx, p):
+    ctx.set_decode_path(p)
+    try:
+        yield ctx
+    finally:
+        ctx.set_decode_path(0)
+
+
+def eliminate(ctx, pieces_t, k):
+    import torch
+
+    from rlnc_amd import batch
+
+    nobj, m, _ = pieces_t.shape
+    T = torch.full((nobj, k, m), 0xAA, dtype=torch.uint8, device="cuda:0")
+    ps = torch.full((nobj, m), -1, dtype=torch.int32, device="cuda:0")
+    rk = torch.full((nobj,), -1, dtype=torch.int32, device="cuda:0")
+    batch.decode_batch_eliminate(pieces_t, k, T, ps, rk, ctx)
+    return host(T), host(ps), host(rk)
+
+
+def check_eliminate(ctx, co, L=4, pad_pieces=0, models=None):
+    """co [nobj][m][k] coefficient vectors -> mode-1 elimination on the device == the model, object by object.
+    pad_pieces: extra pieces per object beyond the m decoded (a non-dense object stride); models: the objects' models
+    when they are already known."""
+    nobj, m, k = co.shape
+    rng = np.random.default_rng(k * 1000 + m)
+    pieces = rng.integers(0, 256, (nobj, m + pad_pieces, k + L), dtype=np.uint8)
+    pieces[:, :m, :k] = co
+    T, ps, rk = eliminate(ctx, dev(pieces)[:, :m], k)
+    if models is None:
+        models = [true_rank_model(k, co[o]) for o in range(nobj)]
+    for o, (st, rank, Tm, _) in enumerate(models):
+        assert list(ps[o]) == st, o
+        assert rk[o] == rank, o
+        assert np.array_equal(T[o], Tm), o
+    return models
+
+
+def combos(rng, basis, n):
+    """n random GF(2^8) combinations of the basis rows."""
+    return np_matmul(rng.integers(0, 256, (n, basis.shape[0]), dtype=np.uint8), basis)
+
+
+def planted(rng, k, m):
+    """Dense vectors with planted duplicates, multiples and sums of earlier pieces."""
+    co = rng.integers(0, 256, (m, k), dtype=np.uint8)
+    for i in range(3, m, 7):
+        a, b = rng.integers(0, i, 2)
+        co[i] = [co[a], MUL[int(rng.integers(2, 256))][co[a]], co[a] ^ co[b]][i % 3]
+    return co
+
+
+def block_cases(rng, k, m, B):
+    """Three objects of m pieces whose dependencies sit on the block boundaries (pieces B at a time):
+    a  block 0 spans only 8 dimensions (a zero piece, a duplicate inside the block); block 1 is useless as a whole
+       (c = 0: combinations, a multiple of an earlier block's piece, a zero piece); later blocks are dense;
+    b  dense with a zero piece and a duplicate: rank k is reached inside block 0, ReceivedAllPieces from there on;
+    c  block 0 spans 15 dimensions; block 1 starts with a multiple of an earlier block's piece, a new piece, the XOR
+       of that new piece and a stored one, a zero piece, then dense pieces: rank k is reached inside block 1."""
+    n = max(m, 3 * B)
+    a = np.zeros((n, k), np.uint8)
+    basis = rng.integers(0, 256, (8, k), dtype=np.uint8)
+    a[:B] = combos(rng, basis, B)
+    a[1] = 0
+    a[5] = a[2]
+    a[B:2 * B] = combos(rng, basis, B)
+    a[B] = MUL[0x1D][a[3]]
+    a[B + 2] = 0
+    a[2 * B:] = rng.integers(0, 256, (n - 2 * B, k), dtype=np.uint8)
+    b = rng.integers(0, 256, (n, k), dtype=np.uint8)
+    b[3] = 0
+    b[6] = b[4]
+    b[B] = MUL[7][b[1]]
+    c = np.zeros((n, k), np.uint8)
+    c[:B] = combos(rng, rng.integers(0, 256, (15, k), dtype=np.uint8), B)
+    c[B:] = rng.integers(0, 256, (n - B, k), dtype=np.uint8)
+    c[B] = MUL[0x53][c[2]]
+    c[B + 2] = c[3] ^ c[B + 1]
+    c[B + 3] = 0
+    return np.stack([a[:m], b[:m], c[:m]])
+
+
+# ---- path 8: the workspace-resident kernels at every shape -------------------------------------------------------------
+
+def test_small_shapes(ctx1):
+    with path(ctx1, LARGE):
+        models = check_eliminate(ctx1, np.stack([FIXTURE, FIXTURE[::-1], FIXTURE[[2, 3, 0, 1]]]))
+        assert models[0][0] == [OK, OK, OK, NOT_USEFUL] and models[0][1] == 3
+        models = check_eliminate(ctx1, np.array([[[0], [5], [7]], [[9], [0], [1]], [[0], [0], [0]]], np.uint8))
+        assert models[0][0] == [NOT_USEFUL, OK, RECEIVED_ALL]
+        rng = np.random.default_rng(1)
+        models = check_eliminate(ctx1, rng.integers(0, 256, (3, 5, 12), dtype=np.uint8))  # m < k, m < B
+        assert all(mdl[1] == 5 for mdl in models)
+
+
+@pytest.mark.parametrize("which", ["B-1", "B", "B+1", "2B+3"])
+def test_block_boundaries(ctx1, which):
+    k = 24
+    B = block_pieces(k, 67)
+    assert B == 32 and block_pieces(k, 31) == B  # every m of this test is cut into blocks of 32
+    m = {"B-1": B - 1, "B": B, "B+1": B + 1, "2B+3": 2 * B + 3}[which]
+    co = block_cases(np.random.default_rng(m), k, m, B)
+    with path(ctx1, LARGE):
+        (sa, ra, _, _), (sb, rb, _, _), (sc, rc, _, _) = check_eliminate(ctx1, co)
+    # the inputs do what their description says
+    assert sa[1] == NOT_USEFUL and sa[5] == NOT_USEFUL and sa[:B].count(OK) == min(8, ra)
+    assert rb == k and sb[3] == NOT_USEFUL and sb[6] == NOT_USEFUL and sb.index(RECEIVED_ALL) < B
+    assert set(sb[sb.index(RECEIVED_ALL):]) == {RECEIVED_ALL}
+    assert sc[:B].count(OK) == 15
+    if m > B:
+        assert sb[B:] == [RECEIVED_ALL] * (m - B)  # a block met at rank k
+        assert sc[B] == NOT_USEFUL
+    if m == 2 * B + 3:
+        assert sa[B:2 * B] == [NOT_USEFUL] * B and sa[2 * B:] == [OK] * 3  # a whole block with no new row
+        assert sc[B + 1] == OK and sc[B + 2] == NOT_USEFUL and sc[B + 3] == NOT_USEFUL
+        assert rc == k and B < sc.index(RECEIVED_ALL) < 2 * B and sc[2 * B:] == [RECEIVED_ALL] * 3
+
+
+@pytest.mark.parametrize("k,m,nobj,density", [(16, 48, 64, 2), (32, 64, 16, 3)])
+def test_sparse(ctx1, k, m, nobj, density):
+    rng = np.random.default_rng(k)
+    with path(ctx1, LARGE):
+        check_eliminate(ctx1, np.stack([sparse_vectors(rng, k, m, density) for _ in range(nobj)]))
+
+
+def test_strided_objects_and_k_not_a_multiple_of_4(ctx1):
+    rng = np.random.default_rng(33)
+    with path(ctx1, LARGE):
+        check_eliminate(ctx1, np.stack([sparse_vectors(rng, 22, 30, 3) for _ in range(5)]), L=7, pad_pieces=3)
+
+
+@functools.lru_cache(maxsize=None)
+def beyond_lds_object():
+    """The object of test_host_fallback_beyond_lds (tests/test_gpu_true_rank.py): k = 300, m = 310, three planted
+    dependencies.  (k, m, data, coding vectors, model), computed once and left unchanged."""
+    k, m = 300, 310
+    rng = np.random.default_rng(300)
+    data = rng.integers(0, 256, k * 16 - 5, dtype=np.uint8)
+    co = rng.integers(0, 256, (m, k), dtype=np.uint8)
+    co[5] = co[2]
+    co[100] = co[7] ^ co[50]
+    co[200] = MUL[0x1D][co[150]]
+    return k, m, data, co, true_rank_model(k, co)
+
+
+def test_rows_wider_than_a_column_chunk(ctx1):
+    k, m, _, co, model = beyond_lds_object()
+    with path(ctx1, LARGE):
+        (st, rank, _, _), = check_eliminate(ctx1, co[None], models=[model])
+    assert rank == k and st.count(NOT_USEFUL) == 3 and st[-1] == RECEIVED_ALL
+
+
+def test_dense_two_objects_k520(ctx1):
+    rng = np.random.default_rng(520)
+    with path(ctx1, LARGE):
+        models = check_eliminate(ctx1, rng.integers(0, 256, (2, 530, 520), dtype=np.uint8))
+    assert all(mdl[1] == 520 for mdl in models)
+
+
+def test_sparse_k1030_crosses_column_chunks(ctx1):
+    """D = 258 + 275 = 533 dwords: nine 64-dword column chunks of the reduce and update grids, the last one partial."""
+    rng = np.random.default_rng(1030)
+    with path(ctx1, LARGE):
+        check_eliminate(ctx1, sparse_vectors(rng, 1030, 1100, 4)[None])
+
+
+# ---- path 7: the device for every shape ----------------------------------------------------------------------------
+
+def test_device_any_keeps_the_lds_kernel_for_small_shapes(ctx1):
+    rng = np.random.default_rng(16)
+    co = np.stack([sparse_vectors(rng, 16, 24, 2), rng.integers(0, 256, (24, 16), dtype=np.uint8)])
+    with path(ctx1, DEVICE_ANY):
+        check_eliminate(ctx1, co)
+
+
+def test_device_any_eliminates_beyond_lds(ctx1):
+    from rlnc_amd.errors import RLNCError
+
+    k, m, _, co, model = beyond_lds_object()
+    with path(ctx1, DEVICE_ANY):
+        check_eliminate(ctx1, co[None], models=[model])
+    with pytest.raises(RLNCError) as ei:  # path 0 answers as before
+        check_eliminate(ctx1, co[None], models=[model])
+    assert ei.value == RLNCError.InvalidArgument
+
+
+def test_device_any_decodes_beyond_lds(ctx1):
+    import torch
+
+    from rlnc_amd import batch
+
+    k, m, data, co, model = beyond_lds_object()
+    L = 16
+    src = npo.pad(data, k)
+    pieces = dev(np.concatenate([co, np_matmul(co, src)], axis=1)[None])
+    with path(ctx1, DEVICE_ANY):
+        decoded = torch.zeros((1, k, L), dtype=torch.uint8, device="cuda:0")
+        ps_d = torch.full((1, m), -1, dtype=torch.int32, device="cuda:0")
+        os_d = torch.full((1,), -1, dtype=torch.int32, device="cuda:0")
+        dl_d = torch.full((1,), -1, dtype=torch.int64, device="cuda:0")
+        batch.decode_batch_device(pieces, k, decoded, ps_d, os_d, dl_d, ctx1)
+        assert list(host(ps_d)[0]) == model[0] and host(os_d)[0] == 0 and int(host(dl_d)[0]) == data.size
+        assert np.array_equal(host(decoded)[0], src)
+        decoded2 = torch.zeros_like(decoded)
+        pst, ost, dl = batch.decode_batch(pieces, k, decoded2, ctx1)
+        assert list(pst[0]) == model[0] and ost[0] == 0 and int(dl[0]) == data.size
+        assert np.array_equal(host(decoded2)[0], src)
+
+
+def test_device_any_ragged(ctx1):
+    """The shape list of tests/test_gpu_true_rank.py::test_decode_ragged, the k = 300 object on the stream."""
+    import torch
+
+    from rlnc_amd import batch
+
+    rng = np.random.default_rng(6)
+    shapes = [(6, 4, 8, "fixture"), (16, 20, 100, 2), (32, 40, 64, "planted"), (64, 70, 32, "dense"), (130, 140, 16, 3),
+              (300, 304, 16, "dense")]
+    objs, want = [], []
+    for k, m, L, kind in shapes:
+        data = rng.integers(0, 256, k * L - 2, dtype=np.uint8)
+        src = npo.pad(data, k)
+        co = (FIXTURE if kind == "fixture" else planted(rng, k, m) if kind == "planted" else
+              rng.integers(0, 256, (m, k), dtype=np.uint8) if kind == "dense" else sparse_vectors(rng, k, m, kind))
+        pieces = np.concatenate([co, np_matmul(co, src)], axis=1)
+        objs.append((dev(pieces), k, torch.zeros((k, L), dtype=torch.uint8, device="cuda:0")))
+        want.append((data, src, true_rank_model(k, co)))
+    with path(ctx1, DEVICE_ANY):
+        ps, os_, dl = batch.decode_ragged(objs, ctx1)
+        ps, os_, dl = host(ps), host(os_), host(dl)
+    at = 0
+    for i, ((k, m, L, _), (data, src, (st, rank, _, _))) in enumerate(zip(shapes, want)):
+        assert list(ps[at:at + m]) == st, i
+        at += m
+        if rank == k:
+            assert os_[i] == 0 and dl[i] == data.size, i
+            assert np.array_equal(host(objs[i][2]), src), i
+        else:
+            assert os_[i] == NOT_ALL_YET, i
+    assert want[0][2][1] == 3 and want[-1][2][1] == 300
+
+
+def test_device_any_host_stream(ctx1):
+    k, m, data, co, model = beyond_lds_object()
+    L = 16
+    src = npo.pad(data, k)
+    pieces = np.ascontiguousarray(np.concatenate([co, np_matmul(co, src)], axis=1)[None])
+    decoded = np.zeros((1, k, L), np.uint8)
+    ps = np.full((1, m), -1, np.int32)
+    os_ = np.full(1, -1, np.int32)
+    dl = np.zeros(1, np.uint64)
+    with path(ctx1, DEVICE_ANY):
+        st = ctx1.lib.rlnc_decode_host_stream(ctx1.h, C.c_void_p(pieces.ctypes.data), m * (k + L), k, L, m, 1,
+                                              C.c_void_p(decoded.ctypes.data), ps.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              os_.ctypes.data_as(C.POINTER(C.c_int32)),
+                                              dl.ctypes.data_as(C.POINTER(C.c_uint64)), 1)
+    assert st == 0
+    assert list(ps[0]) == model[0] and os_[0] == 0 and int(dl[0]) == data.size
+    assert np.array_equal(decoded[0], src)
+
+
+# ---- path rules ------------------------------------------------------------------------------------------------------
+
+def test_path_rules():
+    import torch
+
+    import rlnc_amd
+    from rlnc_amd import batch
+    from rlnc_amd.errors import RLNCError
+
+    ctx = rlnc_amd.Context(0)  # rank mode 0
+    with pytest.raises(RLNCError) as ei:
+        ctx.set_decode_path(9)
+    assert ei.value == RLNCError.InvalidArgument
+    rng = np.random.default_rng(21)
+    k, L = 6, 32
+    src = npo.pad(rng.integers(0, 256, k * L - 3, dtype=np.uint8), k)
+    pieces = dev(npo.encode(src, FIXTURE)[None])
+    dec = torch.zeros((1, k, L), dtype=torch.uint8, device="cuda:0")
+    before = batch.decode_batch(pieces, k, dec, ctx)
+    for p in (DEVICE_ANY, LARGE):  # true-rank kernels: refused in mode 0, no silent fallback
+        ctx.set_decode_path(p)
+        with pytest.raises(RLNCError) as ei:
+            batch.decode_batch(pieces, k, dec, ctx)
+        assert ei.value == RLNCError.InvalidArgument
+        with pytest.raises(RLNCError) as ei:
+            batch.decode_ragged([(pieces[0], k, dec[0])], ctx)
+        assert ei.value == RLNCError.InvalidArgument
+    ctx.set_decode_path(0)
+    after = batch.decode_batch(pieces, k, dec, ctx)
+    for a, b in zip(before, after):
+        assert np.array_equal(a, b)
+    assert list(after[0][0]) == [OK, OK, OK, OK]  # the reference's answer on the fixture, not the true rank's
+
+
+# ---- capture ----------------------------------------------------------------------------------------------------------
+
+def test_decode_batch_device_under_graph_capture():
+    import torch
+
+    import rlnc_amd
+    from rlnc_amd import batch
+
+    k, L = 24, 64
+    B = block_pieces(k, 67)
+    m = 2 * B + 3
+    rng = np.random.default_rng(99)
+
+    def make(seed):
+        co = block_cases(np.random.default_rng(seed), k, m, B)
+        out = []
+        for o in range(co.shape[0]):
+            data = rng.integers(0, 256, k * L - 1 - o, dtype=np.uint8)
+            src = npo.pad(data, k)
+            out.append((data, src, npo.encode(src, co[o]), true_rank_model(k, co[o])))
+        return out
+
+    def check(objs, dec, pst, ost, dl):
+        for o, (data, src, _, (st, rank, _, _)) in enumerate(objs):
+            assert list(pst[o]) == st, o
+            if rank == k:
+                assert ost[o] == 0 and int(dl[o]) == data.size, o
+                assert np.array_equal(dec[o], src), o
+            else:
+                assert ost[o] == NOT_ALL_YET, o
+
+    first = make(1)
+    nobj = len(first)
+    pieces = dev(np.stack([x[2] for x in first]))
+
+    def outputs():
+        return (torch.zeros((nobj, k, L), dtype=torch.uint8, device="cuda:0"),
+                torch.full((nobj, m), -1, dtype=torch.int32, device="cuda:0"),
+                torch.full((nobj,), -1, dtype=torch.int32, device="cuda:0"),
+                torch.full((nobj,), -1, dtype=torch.int64, device="cuda:0"))
+
+    ctx = rlnc_amd.Context(0)  # its workspaces become bound to the graph
+    ctx.set_rank_mode(1)
+    ctx.set_decode_path(LARGE)
+    eager = outputs()
+    batch.decode_batch_device(pieces, k, *eager, ctx)  # the eager run of the shape: workspaces grow here
+    torch.cuda.synchronize()
+    check(first, *[host(t) for t in eager])
+    cap = outputs()
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g, stream=s):
+            batch.decode_batch_device(pieces, k, *cap, ctx)
+    for seed in (2, 3):  # fresh input in the same buffers
+        objs = make(seed)
+        pieces.copy_(dev(np.stack([x[2] for x in objs])))
+        for t in cap:
+            t.fill_(-1 if t.dtype != torch.uint8 else 0)
+        g.replay()
+        torch.cuda.synchronize()
+        check(objs, *[host(t) for t in cap])
