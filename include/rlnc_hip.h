@@ -360,7 +360,9 @@ int rlnc_recode_batch_sparse(rlnc_context *ctx, const uint8_t *pieces_dev, size_
  * row order.  pieces_obj_stride = bytes between objects' first pieces (0 = m*(k+L), i.e. dense; a larger
  * stride decodes from the first m of more coded pieces in place).  Host outputs (each may be NULL): piece_status [obj][m] (status of each decode() call),
  * object_status [obj] (Ok / NotAllPiecesReceivedYet / InvalidDecodedDataFormat of get_decoded_data),
- * data_len [obj] (unpadded length when Ok).  Synchronous. */
+ * data_len [obj] (unpadded length when Ok).  data_len is written for every object: 0 for one that is not Ok (rank < k
+ * or no valid marker), here and in rlnc_decode_batch_device, rlnc_decode_batch_apply / _apply_planned and
+ * rlnc_decode_ragged.  Synchronous. */
 int rlnc_decode_batch(rlnc_context *ctx, const uint8_t *pieces_dev, size_t pieces_obj_stride, size_t k, size_t L,
                       size_t m, size_t num_objects, uint8_t *decoded_dev, int32_t *piece_status,
                       int32_t *object_status, uint64_t *data_len);

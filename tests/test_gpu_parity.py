@@ -31,6 +31,12 @@ def ctx():
     c.set_kernel_variant(DEFAULT_VARIANT, 0)
 
 
+def prefilled(shape, seed=0):
+    """An output buffer that is neither zero nor constant (every byte 1..255 from a seeded generator): a kernel that
+    XORs into its output, skips a row or leaves a byte unwritten no longer passes on np.zeros."""
+    return dev(np.random.default_rng(0xF111 + seed).integers(1, 256, shape, dtype=np.uint8))
+
+
 # ------------------------------------------------------------------------------------------------
 # L1 primitives (simd/mod.rs:18-119): all scalars incl. the 0/1 early-outs, aligned and unaligned
 # ------------------------------------------------------------------------------------------------
@@ -57,6 +63,7 @@ def test_primitives(ctx, n, off):
         tb[off:] = dev(b)
         batch.add_vectors(vb, va, ctx)
         assert np.array_equal(host(vb), a ^ b)
+        assert not host(ta[:off]).any() and not host(tb[:off]).any()  # the bytes before the views: untouched
 
 
 # ------------------------------------------------------------------------------------------------
@@ -79,7 +86,7 @@ def test_matmul(ctx, variant, n_out, n_in, W, nobj):
     if n_out > 1:
         coef[:, 1, ::2] = 0
     inp = rng.integers(0, 256, (nobj, n_in, W), dtype=np.uint8)
-    out = dev(np.zeros((nobj, n_out, W), np.uint8))
+    out = prefilled((nobj, n_out, W), n_out + W)
     ctx.set_kernel_variant(variant, 0)
     try:
         batch.matmul(dev(coef), dev(inp), out, ctx)
@@ -108,7 +115,7 @@ def test_matmul_bitsliced(ctx, variant, n_out, n_in, W, nobj):
     coef[:, -1, :3] = [0, 2, 0x80][: min(3, n_in)]
     inp = rng.integers(0, 256, (nobj, n_in, W), dtype=np.uint8)
     inp[:, 0, :256] = np.arange(256, dtype=np.uint8)  # every byte value against every coefficient row
-    out = dev(np.zeros((nobj, n_out, W), np.uint8))
+    out = prefilled((nobj, n_out, W), n_out + W)
     ctx.set_kernel_variant(variant, 0)
     try:
         batch.matmul(dev(coef), dev(inp), out, ctx)
@@ -135,7 +142,7 @@ def test_matmul_eight_wave_tiles(ctx, n_out, n_in, W, nobj):
     coef[:, 33 % n_out, : min(3, n_in)] = [0, 2, 0x80][: min(3, n_in)]
     inp = rng.integers(0, 256, (nobj, n_in, W), dtype=np.uint8)
     inp[:, 0, :256] = np.arange(256, dtype=np.uint8)
-    out = dev(np.zeros((nobj, n_out, W), np.uint8))
+    out = prefilled((nobj, n_out, W), n_out + W)
     ctx.set_kernel_variant(8, 0)
     try:
         batch.matmul(dev(coef), dev(inp), out, ctx)
@@ -170,7 +177,7 @@ def test_matmul_column_runs(ctx, run, n_out, n_in, W, nobj):
     coef[:, -1, :] = 0
     inp = rng.integers(0, 256, (nobj, n_in, W), dtype=np.uint8)
     inp[:, 0, :256] = np.arange(256, dtype=np.uint8)
-    out = dev(np.zeros((nobj, n_out, W), np.uint8))
+    out = prefilled((nobj, n_out, W), n_out + W)
     ctx.set_kernel_variant(9, 0)
     ctx.set_column_run(run)
     try:
@@ -191,7 +198,7 @@ def test_matmul_every_coefficient_eight_waves(ctx):
     coef = np.arange(256, dtype=np.uint8).reshape(1, 64, 4)
     inp = rng.integers(0, 256, (1, 4, 8192), dtype=np.uint8)
     inp[0, :, :256] = np.arange(256, dtype=np.uint8)
-    out = dev(np.zeros((1, 64, 8192), np.uint8))
+    out = prefilled((1, 64, 8192))
     ctx.set_kernel_variant(8, 0)
     try:
         batch.matmul(dev(coef), dev(inp), out, ctx)
@@ -211,7 +218,7 @@ def test_matmul_every_coefficient(ctx, variant):
     coef = np.arange(256, dtype=np.uint8).reshape(1, 16, 16)
     inp = rng.integers(0, 256, (1, 16, 16384), dtype=np.uint8)
     inp[0, :, :256] = np.arange(256, dtype=np.uint8)
-    out = dev(np.zeros((1, 16, 16384), np.uint8))
+    out = prefilled((1, 16, 16384))
     ctx.set_kernel_variant(variant, 0)
     try:
         batch.matmul(dev(coef), dev(inp), out, ctx)
@@ -264,7 +271,7 @@ def test_matmul_tile_caps(ctx, tile):
     rng = np.random.default_rng(tile)
     coef = rng.integers(0, 256, (1, 40, 12), dtype=np.uint8)
     inp = rng.integers(0, 256, (1, 12, 4096 + 16), dtype=np.uint8)
-    out = dev(np.zeros((1, 40, 4096 + 16), np.uint8))
+    out = prefilled((1, 40, 4096 + 16), tile)
     ctx.set_kernel_variant(0, tile)
     try:
         batch.matmul(dev(coef), dev(inp), out, ctx)
@@ -1037,7 +1044,7 @@ def test_decode_small_objects_marker_outcomes(ctx, k):
     src_d = dev(src.reshape(nobj, k, L))
     pieces = torch.empty((nobj, k, k + L), dtype=torch.uint8, device=src_d.device)
     batch.encode_batch(src_d, dev(co), pieces, ctx)
-    decoded = dev(np.zeros((nobj, k, L), np.uint8))
+    decoded = prefilled((nobj, k, L), k)
     pst, ost, dl = batch.decode_batch(pieces, k, decoded, ctx)
     got = host(decoded).reshape(nobj, k * L)
     for o in range(nobj):

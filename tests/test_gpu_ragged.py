@@ -38,6 +38,11 @@ def ctx():
     return rlnc_amd.Context(0)
 
 
+def prefilled(shape, seed=0):
+    """An output tensor that is neither zero nor constant: bytes 1..255 from a seeded generator."""
+    return dev(np.random.default_rng(0xF111 + seed).integers(1, 256, shape, dtype=np.uint8))
+
+
 def _pieces(orc, rng, k, L, m, dep, sparse, valid):
     """m received pieces of one object: random source (Encoder::new-padded when `valid`), coefficients with
     `sparse` zeros and a `dep` fraction of pieces that are combinations of earlier ones."""
@@ -69,7 +74,7 @@ def test_decode_ragged_many_shapes_vs_oracle(ctx, orc):
             data, pc = _pieces(orc, rng, k, L, m, dep, sparse, valid)
             buf = torch.zeros((m, k + L + pad), dtype=torch.uint8, device="cuda:0")
             buf[:, : k + L] = dev(pc)
-            dec = torch.zeros((k, L), dtype=torch.uint8, device="cuda:0")
+            dec = prefilled((k, L), si * 100 + o)
             objs.append((buf[:, : k + L], k, dec))
             meta.append((k, L, m, data, pc))
             keep.append(buf)
@@ -104,8 +109,8 @@ def test_decode_ragged_matches_uniform_batch(ctx, orc):
     src = np.stack([orc.pad(rng.integers(0, 256, k * L - 5, dtype=np.uint8), k) for _ in range(B)])
     co = rng.integers(0, 256, (B, m, k), dtype=np.uint8)
     pieces = dev(np.stack([orc.encode(src[o], co[o]) for o in range(B)]))
-    d1 = torch.zeros((B, k, L), dtype=torch.uint8, device="cuda:0")
-    d2 = torch.zeros_like(d1)
+    d1 = prefilled((B, k, L), 1)
+    d2 = prefilled((B, k, L), 2)
     ps1, os1, dl1 = batch.decode_ragged([(pieces[o], k, d1[o]) for o in range(B)], ctx)
     ps2 = torch.empty((B, m), dtype=torch.int32, device="cuda:0")
     os2 = torch.empty(B, dtype=torch.int32, device="cuda:0")
@@ -136,7 +141,7 @@ def test_recode_ragged_many_shapes_vs_oracle(ctx, orc, seed):
             r[0] = 0
             buf = torch.zeros((n, k + L + pad), dtype=torch.uint8, device="cuda:0")
             buf[:, : k + L] = dev(coded)
-            out = torch.zeros((cnt, k + L + pad), dtype=torch.uint8, device="cuda:0")
+            out = prefilled((cnt, k + L + pad), k + cnt)
             objs.append((buf[:, : k + L], dev(r), out[:, : k + L], k))
             want.append([orc.recode(coded, k + L, k, r[i]) for i in range(cnt)])
     batch.recode_ragged(objs, ctx)
@@ -162,7 +167,7 @@ def test_encode_ragged_many_shapes_vs_oracle(ctx, orc):
             co = rng.integers(0, 256, (n, k), dtype=np.uint8)
             co[0] = 0
             co[-1] = 1
-            pc = torch.zeros((n, k + L), dtype=torch.uint8, device="cuda:0")
+            pc = prefilled((n, k + L), k + n)
             objs.append((dev(src), dev(co), pc))
             want.append(orc.encode(src, co))
     batch.encode_ragged(objs, ctx)
