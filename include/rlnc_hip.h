@@ -51,6 +51,19 @@
  *     decode path 7 is set (rlnc_set_decode_path): then a second set of kernels keeps the same rows in a device
  *     workspace, takes the pieces B <= 32 at a time (three launches per block, one at the end, none synchronising) and
  *     produces the same T, statuses and rank for k <= 4096, m <= 8192.
+ *   - Decode streams.  rlnc_decode_stream_* keep the rank-mode-1 decoder state of num_objects objects (the rows,
+ *     pivots, statuses and counters of "Rank mode") in a caller-owned device buffer between calls: a receiver pushes
+ *     pieces as they arrive, per object, instead of re-running an elimination over every prefix.  Slot t of object o
+ *     is piece t of that object in the caller's pieces [obj][m][k+L] buffer; the caller fills slots in order and says,
+ *     in an int32 device array, how many of each object are filled.  A push advances every object to that count
+ *     (capped by m and by max_new pieces per object and call) and leaves exactly the state a fresh mode-1 decoder has
+ *     after decode() of the same slots in order -- the same statuses, rank and T, however the pieces were split over
+ *     pushes.  The kernels are those of decode paths 7 and 8 with the block taken per object from the state
+ *     (rlnc_amd/csrc/rank_large.hip); k <= 4096, m <= 8192.  Not covered: the slot capacity m counts every arrival,
+ *     useless ones included (a stream that may see many dependent pieces wants m well above k); small generations run
+ *     these workspace kernels too, not the LDS kernel of paths 0 and 2; the reference rank mode has no stream form
+ *     (a context in mode 0 is refused).  Measured on one MI355X (profiles/r12_decode_stream.jsonl): see DESIGN.md
+ *     §4.2.4.
  *   - Sparse coding vectors.  The *_sparse calls take a coefficient matrix as two arrays with a fixed number w of
  *     entries per output row: idx int32 [obj][n_out][w], the source-row index of each entry, and val uint8
  *     [obj][n_out][w], its coefficient.  The dense row c they stand for is c[j] = XOR of val[t] over all t with
@@ -400,6 +413,45 @@ int rlnc_decode_batch_apply_planned(rlnc_context *ctx, const uint8_t *pieces_dev
                                     size_t L, size_t m, size_t num_objects, const uint8_t *T_dev,
                                     const int32_t *rank_dev, uint8_t *decoded_dev, int32_t *object_status_dev,
                                     int64_t *data_len_dev, const void *plan_dev);
+
+/* ---- decode streams: the device decode, resumable ("Decode streams" above) ----------------------------------------
+ * A slot of a stream's status array that no push has answered yet. */
+#define RLNC_STATUS_PENDING (-1)
+/* Bytes of the state buffer of num_objects objects of generation size k with m piece slots each: a multiple of 16;
+ * 0 outside the limits, exactly where rlnc_decode_large_workspace_bytes is 0.  Pure: needs no context and no GPU. */
+size_t rlnc_decode_stream_state_bytes(size_t k, size_t m, size_t num_objects);
+/* Starts a stream in state_dev (caller-owned device memory, 16-byte aligned, state_bytes >= the above): rank, pieces
+ * answered and target of every object become 0.  One asynchronous launch on the context's stream.  The library
+ * remembers each init by the state buffer's address with (device, k, m, num_objects), as it remembers plan buffers;
+ * push and snapshot with other values, or on a buffer never initialised, return RLNC_ERR_INVALID_ARGUMENT (it keeps
+ * the 256 most recently initialised buffers: a stream is many objects, a process needs few of them).  What it
+ * cannot see is the caller's contract: the state buffer stays alive and unwritten by anyone else between the calls
+ * (a buffer freed and reallocated at the same address must be initialised again), and the slots below avail are not
+ * rewritten once they have been pushed.  All three calls return RLNC_ERR_INVALID_ARGUMENT on a context in rank mode 0
+ * (no silent fallback), for a null handle or state, a misaligned or short state buffer and a shape outside the
+ * limits; the decode path setting is irrelevant. */
+int rlnc_decode_stream_init(rlnc_context *ctx, void *state_dev, size_t state_bytes, size_t k, size_t m,
+                            size_t num_objects);
+/* Object o advances from done_o, the slots answered so far, to min(max(avail_dev[o], done_o), m, done_o + max_new):
+ * those slots of pieces_dev (addressed as in rlnc_decode_batch_eliminate: object stride in bytes, 0 = m*(k+L)) are
+ * pushed to its decoder in order.  An avail below done_o changes nothing; one above m is clamped.  Asynchronous on
+ * the context's stream, never synchronises and grows no context workspace, so it can be captured into a HIP graph
+ * and replayed while avail_dev changes between replays.  avail_dev (int32 [num_objects]) is read by the call's first
+ * launch only: the caller may overwrite it as soon as the call returns.  1 + 3 * ceil(min(max_new, m) / B) launches
+ * (B <= 32 pieces per block), plus one when rank_dev or answered_dev (int32 [num_objects], each may be NULL) are
+ * asked for: every object's rank and done_o after the push.  An object whose rank is k still consumes its slots
+ * (ReceivedAllPieces).  k == 0 PieceCountZero, then L == 0 PieceLengthZero; max_new == 0 or num_objects == 0: RLNC_OK,
+ * nothing launched. */
+int rlnc_decode_stream_push(rlnc_context *ctx, void *state_dev, size_t state_bytes, const uint8_t *pieces_dev,
+                            size_t pieces_obj_stride, size_t k, size_t L, size_t m, size_t num_objects,
+                            const int32_t *avail_dev, size_t max_new, int32_t *rank_dev, int32_t *answered_dev);
+/* What the stream holds now, in the layout of rlnc_decode_batch_eliminate (one launch; any output may be NULL; the
+ * state is not modified and a later push continues from it): T_dev [obj][k][m], rows in pivot order, rows >= rank
+ * and columns >= done_o zero; piece_status_dev [obj][m], the decoder's answer for the slots below done_o and
+ * RLNC_STATUS_PENDING for the others; rank_dev [obj].  T_dev and rank_dev go straight into rlnc_decode_batch_apply
+ * (NotAllPiecesReceivedYet for an object below rank k). */
+int rlnc_decode_stream_snapshot(rlnc_context *ctx, const void *state_dev, size_t state_bytes, size_t k, size_t m,
+                                size_t num_objects, uint8_t *T_dev, int32_t *piece_status_dev, int32_t *rank_dev);
 
 /* ---- wire formats on the device ------------------------------------------------------------
  * Encoder::new's padded image (encoder.rs:85-106, BOUNDARY_MARKER consts.rs:5) built by a kernel from a byte

@@ -65,6 +65,8 @@ class SparseMatmulDesc(C.Structure):
 # decode paths of rank mode 1 beyond LDS (include/rlnc_hip.h, rlnc_set_decode_path)
 RLNC_DECODE_PATH_DEVICE_ANY = 7
 RLNC_DECODE_PATH_LARGE = 8
+# a decode stream's slot that no push has answered yet (rlnc_decode_stream_snapshot)
+RLNC_STATUS_PENDING = -1
 
 _SIGS = {
     "rlnc_status_name": (C.c_char_p, [C.c_int]),
@@ -144,6 +146,11 @@ _SIGS = {
                                                   vp, vp, vp, C.c_size_t]),
     "rlnc_decode_batch_apply_planned": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                                   vp, vp, vp, vp, vp, vp]),
+    "rlnc_decode_stream_state_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t]),
+    "rlnc_decode_stream_init": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "rlnc_decode_stream_push": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                          C.c_size_t, vp, C.c_size_t, vp, vp]),
+    "rlnc_decode_stream_snapshot": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp]),
     "rlnc_recode_batch": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "rlnc_encode_batch_sparse": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t,
                                            vp]),

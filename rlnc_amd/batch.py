@@ -426,3 +426,101 @@ def decode_ragged(objs, ctx: Context | None = None):
     check(ctx.lib.rlnc_decode_ragged(ctx.h, arr, len(descs), C.c_void_p(ps_t.data_ptr()), C.c_void_p(os_t.data_ptr()),
                                      C.c_void_p(dl_t.data_ptr())), ctx.lib)
     return ps_t, os_t, dl_t
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# decode streams (include/rlnc_hip.h, "Decode streams"): the device decode, resumable -- pieces pushed as they arrive,
+# per object
+# ------------------------------------------------------------------------------------------------------------------
+def state_bytes(k: int, m: int, num_objects: int) -> int:
+    """Device bytes of a decode stream's state for num_objects objects of generation size k with m piece slots each
+    (0: outside the limits, k <= 4096 and m <= 8192).  Needs no GPU."""
+    from ._lib import load
+
+    return int(load().rlnc_decode_stream_state_bytes(k, m, num_objects))
+
+
+class DecodeStream:
+    """The true-rank decoder state of num_objects objects (generation size k, m piece slots each) kept on the device
+    between calls.  Slot t of object o is pieces[o][t] of the caller's pieces [obj][m][k+L] tensor; the caller fills
+    slots in order as pieces arrive and says in `avail` (int32 [obj], device) how many of each object are filled.
+    After any sequence of pushes the state is a fresh mode-1 decoder's after decode() of the same slots in order.
+
+    ctx: a context in rank mode 1 (a context in mode 0 is refused); None: a context of the stream's own, in rank mode 1
+    on torch's current device.  Every call launches on torch's current stream and none synchronises."""
+
+    def __init__(self, k: int, m: int, num_objects: int, ctx: Context | None = None):
+        import torch
+
+        self.k, self.m, self.num_objects = int(k), int(m), int(num_objects)
+        nbytes = state_bytes(self.k, self.m, self.num_objects)
+        assert nbytes > 0, f"a decode stream takes k <= 4096, m <= 8192 and at least one object: {(k, m, num_objects)}"
+        if ctx is None:
+            ctx = Context(torch.cuda.current_device())
+            ctx.set_rank_mode(1)
+        self.ctx = ctx
+        dev = torch.device("cuda", ctx.device)
+        self.state = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        assert self.state.data_ptr() % 16 == 0
+        self._T = None
+        self._rank = None
+        c = _ctx_for(self.state, self.ctx)
+        check(c.lib.rlnc_decode_stream_init(c.h, C.c_void_p(self.state.data_ptr()), nbytes, self.k, self.m,
+                                            self.num_objects), c.lib)
+
+    def _i32(self, t, shape, name):
+        import torch
+
+        assert t.is_cuda and t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+            f"{name}: int32 contiguous device tensor of shape {tuple(shape)} required"
+        return C.c_void_p(t.data_ptr())
+
+    def _pieces(self, pieces):
+        nobj, m, L, obj_stride = _pieces_view(pieces, self.k)
+        import torch
+
+        assert pieces.is_cuda and pieces.dtype == torch.uint8 and (pieces.shape[2] == 1 or pieces.stride(2) == 1)
+        assert (nobj, m) == (self.num_objects, self.m) and L > 0, (tuple(pieces.shape), self.num_objects, self.m)
+        return L, obj_stride
+
+    def push(self, pieces, avail, max_new: int | None = None, rank=None, answered=None) -> None:
+        """Object o advances from the slots answered so far, done_o, to min(max(avail[o], done_o), m, done_o +
+        max_new) (max_new=None: m).  avail may be overwritten as soon as this returns.  rank / answered (int32 [obj]
+        device tensors, optional) receive every object's rank and done_o after the push."""
+        L, obj_stride = self._pieces(pieces)
+        n = (self.num_objects,)
+        av = self._i32(avail, n, "avail")
+        rk = self._i32(rank, n, "rank") if rank is not None else None
+        an = self._i32(answered, n, "answered") if answered is not None else None
+        max_new = self.m if max_new is None else int(max_new)
+        assert max_new >= 0
+        c = _ctx_for(self.state, self.ctx)
+        check(c.lib.rlnc_decode_stream_push(c.h, C.c_void_p(self.state.data_ptr()), self.state.numel(),
+                                            C.c_void_p(pieces.data_ptr()), obj_stride, self.k, L, self.m,
+                                            self.num_objects, av, max_new, rk, an), c.lib)
+
+    def snapshot(self, T=None, piece_status=None, rank=None) -> None:
+        """What the stream holds now (each output optional; the state is not modified): T uint8 [obj][k][m] as
+        decode_batch_eliminate writes it (columns >= done_o zero), piece_status int32 [obj][m] (RLNC_STATUS_PENDING,
+        -1, for the slots not yet answered), rank int32 [obj]."""
+        if T is not None:
+            _chk(T, (self.num_objects, self.k, self.m))
+        ps = self._i32(piece_status, (self.num_objects, self.m), "piece_status") if piece_status is not None else None
+        rk = self._i32(rank, (self.num_objects,), "rank") if rank is not None else None
+        c = _ctx_for(self.state, self.ctx)
+        check(c.lib.rlnc_decode_stream_snapshot(c.h, C.c_void_p(self.state.data_ptr()), self.state.numel(), self.k,
+                                                self.m, self.num_objects,
+                                                C.c_void_p(T.data_ptr()) if T is not None else None, ps, rk), c.lib)
+
+    def apply(self, pieces, decoded, object_status, data_len) -> None:
+        """The data of what was pushed so far: a snapshot into the stream's own T and rank, then decode_batch_apply
+        (decoded [obj][k][L]; object_status int32 [obj]: Ok, NotAllPiecesReceivedYet below rank k, or
+        InvalidDecodedDataFormat; data_len int64 [obj])."""
+        import torch
+
+        self._pieces(pieces)
+        if self._T is None:
+            self._T = torch.empty((self.num_objects, self.k, self.m), dtype=torch.uint8, device=self.state.device)
+            self._rank = torch.empty((self.num_objects,), dtype=torch.int32, device=self.state.device)
+        self.snapshot(T=self._T, rank=self._rank)
+        decode_batch_apply(pieces, self.k, self._T, self._rank, decoded, object_status, data_len, self.ctx)

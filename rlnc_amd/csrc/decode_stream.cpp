@@ -1,0 +1,125 @@
+// decode_stream.cpp — the resumable device decode of librlnc_hip (include/rlnc_hip.h, "Decode streams"): the
+// true-rank decoder state of many objects in a caller-owned device buffer, pushed forward as pieces arrive
+// (rank_large.hip in its stream form; rank_large_kernels.hpp), and the registry of initialised state buffers.
+#include <mutex>
+#include <tuple>
+#include <vector>
+
+#include "context.hpp"
+
+using namespace rlnc::eng;
+
+namespace {
+
+// State buffers initialised by rlnc_decode_stream_init (any context), by address: the device and the shape they were
+// laid out for.  Push and snapshot take a buffer only with exactly those, as the planned products take a plan buffer.
+struct StreamKey {
+    int device;
+    size_t k, m, nobj;
+    auto tie() const { return std::tie(device, k, m, nobj); }
+    bool operator==(const StreamKey &o) const { return tie() == o.tie(); }
+};
+std::mutex g_stream_mu;
+std::vector<std::pair<const void *, StreamKey>> g_streams;  // (state buffer, key), most recent last
+constexpr size_t kStreamRecs = 256;
+
+void remember_stream(const void *state, const StreamKey &key) {
+    std::lock_guard<std::mutex> lock(g_stream_mu);
+    for (auto it = g_streams.begin(); it != g_streams.end(); ++it)
+        if (it->first == state) {
+            g_streams.erase(it);
+            break;
+        }
+    if (g_streams.size() >= kStreamRecs) g_streams.erase(g_streams.begin());
+    g_streams.emplace_back(state, key);
+}
+
+int stream_check(const void *state, const StreamKey &key) {
+    std::lock_guard<std::mutex> lock(g_stream_mu);
+    for (auto it = g_streams.rbegin(); it != g_streams.rend(); ++it)
+        if (it->first == state) {
+            if (it->second == key) return RLNC_OK;
+            break;
+        }
+    return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                     "decode stream state %p was not initialised for this device and shape (k=%zu, m=%zu, %zu objects): "
+                     "call rlnc_decode_stream_init with the arguments of this call",
+                     state, key.k, key.m, key.nobj);
+}
+
+// what init, push and snapshot share: the handle, the state buffer, the shape, the rank mode
+int stream_args(rlnc_context *ctx, const void *state, size_t state_bytes, size_t k, size_t m, size_t nobj) {
+    CHECK_ARG(ctx != nullptr && state != nullptr);
+    CHECK_ARG((reinterpret_cast<uintptr_t>(state) & 15) == 0);
+    if (ctx->rank_mode != RLNC_RANK_MODE_TRUE)
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "a decode stream has true-rank semantics: the context is in rank mode %d (rlnc_set_rank_mode)",
+                         ctx->rank_mode);
+    const size_t need = rlnc::rank_stream_state_bytes(k, m, nobj);
+    if (need == 0)
+        return set_error(RLNC_ERR_INVALID_ARGUMENT, "a decode stream takes k <= %d, m <= %d and at least one object "
+                         "(k=%zu, m=%zu, %zu objects)", rlnc::kLargeMaxK, rlnc::kLargeMaxM, k, m, nobj);
+    CHECK_ARG(state_bytes >= need);
+    return RLNC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t rlnc_decode_stream_state_bytes(size_t k, size_t m, size_t nobj) {
+    return rlnc::rank_stream_state_bytes(k, m, nobj);
+}
+
+int rlnc_decode_stream_init(rlnc_context *ctx, void *state, size_t state_bytes, size_t k, size_t m, size_t nobj) {
+    int st = stream_args(ctx, state, state_bytes, k, m, nobj);
+    if (st || (st = ctx->activate()) || (st = ctx->note_capture())) return st;
+    HIP_TRY(rlnc::launch_rank_stream_init(int(k), int(m), int(nobj), state, state_bytes, ctx->stream));
+    remember_stream(state, StreamKey{ctx->device, k, m, nobj});
+    return RLNC_OK;
+}
+
+int rlnc_decode_stream_push(rlnc_context *ctx, void *state, size_t state_bytes, const uint8_t *pieces,
+                            size_t obj_stride, size_t k, size_t L, size_t m, size_t nobj, const int32_t *avail,
+                            size_t max_new, int32_t *rank_dev, int32_t *answered_dev) {
+    CHECK_ARG(ctx != nullptr);
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    if (L == 0) return RLNC_ERR_PIECE_LENGTH_ZERO;
+    if (max_new == 0 || nobj == 0) return RLNC_OK;
+    CHECK_ARG(pieces != nullptr && avail != nullptr);
+    int st = stream_args(ctx, state, state_bytes, k, m, nobj);
+    if (st) return st;
+    if (obj_stride == 0) obj_stride = m * (k + L);
+    CHECK_ARG(obj_stride >= m * (k + L));
+    if ((st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
+    if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
+    rlnc::RrefParams rp{};
+    rp.pieces = pieces;
+    rp.obj_stride = int64_t(obj_stride);
+    rp.piece_stride = int64_t(k + L);
+    rp.k = int(k);
+    rp.m = int(m);
+    rp.n_obj = int(nobj);
+    HIP_TRY(rlnc::launch_rank_stream_push(rp, state, state_bytes, avail, int(std::min(max_new, m)), rank_dev,
+                                          answered_dev, ctx->stream));
+    return RLNC_OK;
+}
+
+int rlnc_decode_stream_snapshot(rlnc_context *ctx, const void *state, size_t state_bytes, size_t k, size_t m,
+                                size_t nobj, uint8_t *T_dev, int32_t *piece_status_dev, int32_t *rank_dev) {
+    int st = stream_args(ctx, state, state_bytes, k, m, nobj);
+    if (st || (st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
+    if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
+    rlnc::RrefParams rp{};
+    rp.k = int(k);
+    rp.m = int(m);
+    rp.n_obj = int(nobj);
+    rp.T = T_dev;
+    rp.T_obj = int64_t(k * m);
+    rp.status = piece_status_dev;
+    rp.rank = rank_dev;
+    HIP_TRY(rlnc::launch_rank_stream_snapshot(rp, state, state_bytes, ctx->stream));
+    return RLNC_OK;
+}
+
+}  // extern "C"

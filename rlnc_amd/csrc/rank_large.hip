@@ -29,6 +29,15 @@
 // pivot, the status and the normalised row are the model's.  After the update every row has 1 in its own pivot column
 // and 0 in the rest of P, which determines it within the span: the state is the model's state after the same pieces.
 //
+// The stream form (template parameter STREAM; decode streams, rank_large_kernels.hpp): the state outlives the call, and
+// a block is each object's own -- t0 = pieces answered, b = min(B, target - t0), read from the state, where a latch
+// launch at the start of a push left the target.  The proof above is per block and does not say where a block starts,
+// so it holds for these blocks as it stands.  What differs from the one-shot form: an object with b = 0 is idle (every
+// workgroup of it returns before any barrier; its step still sets "rank before" to the rank, or the update would apply
+// the previous block's Q and new rows again), and an object at rank k still has its slots answered by the step
+// (ReceivedAllPieces, pieces answered += b), because the snapshot tells answered slots from pending ones.  The one-shot
+// instantiations keep the instructions they had before the parameter existed.
+//
 // Rules kept by every kernel: no workgroup waits for another; every branch around a barrier is workgroup-uniform, on
 // values read after the previous barrier and passed through readfirstlane; the early return (nothing left to do) comes
 // before any barrier; shared global state is ordered by barriers and kernel boundaries only.
@@ -83,6 +92,16 @@ __device__ __forceinline__ void copy_table(uint32_t *tab) {
 
 __device__ __forceinline__ uint32_t uni(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
+// The stream form of a block (STREAM kernels; rank_large_kernels.hpp, "Decode streams"): the object's own block, from
+// its state instead of the launch's t0 and b -- pieces done .. min(done + B, target) - 1, where the push's latch launch
+// left the target in the state's fourth word.  b <= 0: the object is idle in this block.  Both values are
+// workgroup-uniform: no launch that calls this writes words 2 and 3 before a barrier that follows the call.
+__device__ __forceinline__ void stream_block(const uint32_t *ws, int B, int &t0, int &b) {
+    t0 = __builtin_amdgcn_readfirstlane(int(ws[2]));
+    b = min(B, __builtin_amdgcn_readfirstlane(int(ws[3])) - t0);
+}
+
+template <bool STREAM>
 __global__ __launch_bounds__(256) void gf_rank_large_reduce(LargeParams p) {
     __shared__ uint32_t tab[kTabDwords];
     __shared__ uint2 qh[4][kQTile];
@@ -91,8 +110,13 @@ __global__ __launch_bounds__(256) void gf_rank_large_reduce(LargeParams p) {
     const int kd = (k + 3) >> 2, D = L.D;
     const int o = int(blockIdx.x) / p.chunks, chunk = int(blockIdx.x) % p.chunks;
     uint32_t *ws = p.ws + int64_t(o) * p.ws_obj;
-    const int rank = p.t0 == 0 ? 0 : __builtin_amdgcn_readfirstlane(int(ws[0]));
-    if (rank >= k) return;  // ReceivedAllPieces for the whole block: the step does not run either
+    int t0 = p.t0, b = p.b;
+    if constexpr (STREAM) {
+        stream_block(ws, L.B, t0, b);
+        if (b <= 0) return;  // an idle object: nothing new in this block
+    }
+    const int rank = (!STREAM && t0 == 0) ? 0 : __builtin_amdgcn_readfirstlane(int(ws[0]));
+    if (rank >= k) return;  // ReceivedAllPieces for the whole block: the step only answers
     const int32_t *piv = reinterpret_cast<const int32_t *>(ws + L.piv);
     const uint32_t *R = ws + L.r;
     uint32_t *X = ws + L.x;
@@ -108,8 +132,8 @@ __global__ __launch_bounds__(256) void gf_rank_large_reduce(LargeParams p) {
     for (int j = 0; j < kLargeMaxB / 4; ++j) {
         acc[j] = 0;
         const int t = 4 * j + g;
-        if (t < p.b && act) {
-            const int pi = p.t0 + t;
+        if (t < b && act) {
+            const int pi = t0 + t;
             if (d < kd) {
                 const uint8_t *h = base + int64_t(pi) * p.piece_stride;
                 uint32_t w = 0;
@@ -140,7 +164,7 @@ __global__ __launch_bounds__(256) void gf_rank_large_reduce(LargeParams p) {
 #pragma unroll
                 for (int j = 0; j < kLargeMaxB / 4; ++j) {
                     const int t = 4 * j + gg;
-                    hb[r][j] = (pc[r] >= 0 && t < p.b) ? base[int64_t(p.t0 + t) * p.piece_stride + pc[r]] : uint8_t(0);
+                    hb[r][j] = (pc[r] >= 0 && t < b) ? base[int64_t(t0 + t) * p.piece_stride + pc[r]] : uint8_t(0);
                 }
 #pragma unroll
             for (int r = 0; r < NP; ++r) {
@@ -195,25 +219,43 @@ __global__ __launch_bounds__(256) void gf_rank_large_reduce(LargeParams p) {
 #pragma unroll
         for (int j = 0; j < kLargeMaxB / 4; ++j) {
             const int t = 4 * j + g;
-            if (t < p.b) X[int64_t(t) * D + d] = acc[j];
+            if (t < b) X[int64_t(t) * D + d] = acc[j];
         }
     }
 }
 
+template <bool STREAM>
 __global__ __launch_bounds__(256) void gf_rank_large_step(LargeParams p) {
     extern __shared__ uint32_t lds[];
-    const int k = p.k, m = p.m, b = p.b;
+    const int k = p.k, m = p.m;
     const LargeLayout L = large_layout(k, m);
     const int kd = (k + 3) >> 2, D = L.D;
     uint32_t *ws = p.ws + int64_t(blockIdx.x) * p.ws_obj;
     const int tid = int(threadIdx.x), lane = tid & 63;
-    const int rank0 = p.t0 == 0 ? 0 : __builtin_amdgcn_readfirstlane(int(ws[0]));
-    if (rank0 >= k) {  // nothing to do: the update sees no new rows, the final launch answers ReceivedAllPieces
+    int t0 = p.t0, b = p.b;
+    if constexpr (STREAM) stream_block(ws, L.B, t0, b);
+    const int rank0 = (!STREAM && t0 == 0) ? 0 : __builtin_amdgcn_readfirstlane(int(ws[0]));
+    int32_t *St = reinterpret_cast<int32_t *>(ws + L.st);
+    if constexpr (STREAM) {
+        if (b <= 0) {  // an idle object.  "Rank before" still moves up to the rank: the update takes c = rank - rank
+                       // before and would otherwise apply the previous block's Q and new rows a second time
+            if (tid == 0) ws[1] = uint32_t(rank0);
+            return;
+        }
+        if (rank0 >= k) {  // the block's slots are consumed all the same: the snapshot tells them from pending ones
+            __syncthreads();  // every wave has read the state that thread 0 rewrites
+            for (int tt = tid; tt < b; tt += 256) St[t0 + tt] = RLNC_ERR_RECEIVED_ALL_PIECES;
+            if (tid == 0) {
+                ws[1] = uint32_t(rank0);
+                ws[2] = uint32_t(t0 + b);
+            }
+            return;
+        }
+    } else if (rank0 >= k) {  // nothing to do: the update sees no new rows, the final launch answers ReceivedAllPieces
         if (tid == 0) ws[1] = uint32_t(rank0);
         return;
     }
     int32_t *piv = reinterpret_cast<int32_t *>(ws + L.piv);
-    int32_t *St = reinterpret_cast<int32_t *>(ws + L.st);
     uint32_t *Q = ws + L.q;
     const uint32_t *X = ws + L.x;
     uint32_t *R = ws + L.r;
@@ -319,7 +361,7 @@ __global__ __launch_bounds__(256) void gf_rank_large_step(LargeParams p) {
         pc = __builtin_amdgcn_readfirstlane(pc);
         val = uni(val);
         if (pc < 0) {
-            if (tid == 0) St[p.t0 + t] = RLNC_ERR_PIECE_NOT_USEFUL;
+            if (tid == 0) St[t0 + t] = RLNC_ERR_PIECE_NOT_USEFUL;
             continue;
         }
         // insert: snapshot the earlier new rows' bytes in the pivot column, normalise, clear (a thread owns its columns)
@@ -332,13 +374,13 @@ __global__ __launch_bounds__(256) void gf_rank_large_step(LargeParams p) {
             npiv[c] = pc;
             nrow[c] = t;
             rpiv[t] = pc;
-            St[p.t0 + t] = RLNC_OK;
+            St[t0 + t] = RLNC_OK;
         }
         rows_muladd(t, std::false_type{}, gfinv(tab, val));
         ++c;
         __syncthreads();
     }
-    for (int tt = t + tid; tt < b; tt += 256) St[p.t0 + tt] = RLNC_ERR_RECEIVED_ALL_PIECES;
+    for (int tt = t + tid; tt < b; tt += 256) St[t0 + tt] = RLNC_ERR_RECEIVED_ALL_PIECES;
     // the new rows, their pivots and the older rows' quotients
     for (int s = 0; s < c; ++s) {
         const uint32_t *y = Xs + nrow[s] * D;
@@ -373,7 +415,7 @@ __global__ __launch_bounds__(256) void gf_rank_large_step(LargeParams p) {
     if (tid == 0) {
         ws[1] = uint32_t(rank0);
         ws[0] = uint32_t(rank0 + c);
-        ws[2] = uint32_t(p.t0 + b);
+        ws[2] = uint32_t(t0 + b);
     }
 }
 
@@ -429,6 +471,8 @@ __global__ __launch_bounds__(256) void gf_rank_large_update(LargeParams p) {
     }
 }
 
+// STREAM: the snapshot of a decode stream -- every output optional, RLNC_STATUS_PENDING for the slots not yet answered
+template <bool STREAM>
 __global__ __launch_bounds__(256) void gf_rank_large_final(LargeParams p) {
     __shared__ int32_t colrow[kLargeMaxK];  // stored row of pivot column c, or -1
     __shared__ int32_t ord[kLargeMaxK];     // stored row of T row r
@@ -439,6 +483,8 @@ __global__ __launch_bounds__(256) void gf_rank_large_final(LargeParams p) {
     const int o = int(blockIdx.x) / p.fin_chunks, fc = int(blockIdx.x) % p.fin_chunks;
     const uint32_t *ws = p.ws + int64_t(o) * p.ws_obj;
     const int tid = int(threadIdx.x);
+    if constexpr (STREAM)
+        if (p.T == nullptr && fc != 0) return;  // only T is spread over the row chunks
     const int rank = __builtin_amdgcn_readfirstlane(int(ws[0]));
     const int done = __builtin_amdgcn_readfirstlane(int(ws[2]));
     const int32_t *piv = reinterpret_cast<const int32_t *>(ws + L.piv);
@@ -461,7 +507,10 @@ __global__ __launch_bounds__(256) void gf_rank_large_final(LargeParams p) {
     __syncthreads();
     const int r0 = fc * kFinRows, r1 = min(r0 + kFinRows, k);
     uint8_t *T = p.T + int64_t(o) * p.T_obj;
-    if ((m & 3) == 0 && (reinterpret_cast<uintptr_t>(T) & 3) == 0) {
+    const bool want_T = !STREAM || p.T != nullptr;
+    if (!want_T) {
+        // a snapshot without T
+    } else if ((m & 3) == 0 && (reinterpret_cast<uintptr_t>(T) & 3) == 0) {
         const int mw = m >> 2;
         uint32_t *Tw = reinterpret_cast<uint32_t *>(T);
         for (int idx = tid; idx < (r1 - r0) * mw; idx += 256) {
@@ -476,13 +525,45 @@ __global__ __launch_bounds__(256) void gf_rank_large_final(LargeParams p) {
         }
     }
     if (fc == 0) {
-        for (int t = tid; t < m; t += 256)
-            p.status[int64_t(o) * m + t] = t < done ? St[t] : int32_t(RLNC_ERR_RECEIVED_ALL_PIECES);
-        if (tid == 0) p.rank[o] = rank;
+        if (!STREAM || p.status != nullptr)
+            for (int t = tid; t < m; t += 256)
+                p.status[int64_t(o) * m + t] =
+                    t < done ? St[t] : int32_t(STREAM ? RLNC_STATUS_PENDING : RLNC_ERR_RECEIVED_ALL_PIECES);
+        if (tid == 0 && (!STREAM || p.rank != nullptr)) p.rank[o] = rank;
     }
 }
 
-// the 160 KiB dynamic-LDS attribute of the block step, once per device
+// ---- decode streams: the small launches around the blocks of a push --------------------------------------------------
+// one thread per object; the state words {rank, rank before, done, target} are each object's first four dwords
+
+__global__ __launch_bounds__(256) void gf_rank_stream_init(uint32_t *ws, int64_t ws_obj, int nobj) {
+    const int o = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (o < nobj) *reinterpret_cast<uint4 *>(ws + int64_t(o) * ws_obj) = make_uint4(0u, 0u, 0u, 0u);
+}
+
+// the latch: target = min(max(avail, done), m, done + max_new), kept in the state so that no later launch of the push
+// reads avail.  A done outside [0, m] (a state the library did not write) leaves the object idle.
+__global__ __launch_bounds__(256) void gf_rank_stream_latch(uint32_t *ws, int64_t ws_obj, int nobj,
+                                                           const int32_t *avail, int m, int max_new) {
+    const int o = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (o >= nobj) return;
+    uint32_t *st = ws + int64_t(o) * ws_obj;
+    const int done = int(st[2]);
+    int target = done;
+    if (done >= 0 && done < m) target = min(min(max(avail[o], done), m), done + min(max_new, m - done));
+    st[3] = uint32_t(target);
+}
+
+__global__ __launch_bounds__(256) void gf_rank_stream_progress(const uint32_t *ws, int64_t ws_obj, int nobj,
+                                                              int32_t *rank, int32_t *answered) {
+    const int o = int(blockIdx.x) * 256 + int(threadIdx.x);
+    if (o >= nobj) return;
+    const uint32_t *st = ws + int64_t(o) * ws_obj;
+    if (rank != nullptr) rank[o] = int32_t(st[0]);
+    if (answered != nullptr) answered[o] = int32_t(st[2]);
+}
+
+// the 160 KiB dynamic-LDS attribute of the block step (both forms), once per device
 hipError_t step_attr() {
     static std::mutex mu;
     static bool attr_set[64] = {};
@@ -492,7 +573,10 @@ hipError_t step_attr() {
     if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
     std::lock_guard<std::mutex> lock(mu);
     if (!attr_set[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_rank_large_step),
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_rank_large_step<false>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
+        if (e != hipSuccess) return e;
+        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_rank_large_step<true>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
         if (e != hipSuccess) return e;
         attr_set[dev] = true;
@@ -500,21 +584,21 @@ hipError_t step_attr() {
     return hipSuccess;
 }
 
-}  // namespace
-
-hipError_t launch_rank_large(const RrefParams &rp, void *ws, size_t ws_bytes, hipStream_t s) {
-    if (rp.n_obj <= 0) return hipSuccess;
+// the launches' common part: the shape and workspace checks, the step's LDS attribute, the parameters and the grids
+struct LargeGrids {
+    size_t step_lds;
+    unsigned reduce, step, update, fin;
+};
+hipError_t large_setup(const RrefParams &rp, const void *ws, size_t ws_bytes, LargeParams &p, LargeGrids &g) {
     if (rp.objs != nullptr) return hipErrorInvalidValue;
     const int B = large_block(rp.k, rp.m);
     if (B == 0 || ws == nullptr || (reinterpret_cast<uintptr_t>(ws) & 15) != 0 ||
         ws_bytes < rank_large_workspace_bytes(size_t(rp.k), size_t(rp.m), size_t(rp.n_obj)))
         return hipErrorInvalidValue;
     const LargeLayout L = large_layout(rp.k, rp.m);
-    const size_t step_lds = kLargeStepFixedBytes + size_t(B) * size_t(L.D) * 4;
-    if (step_lds > kRrefMaxLds) return hipErrorInvalidValue;
-    hipError_t e = step_attr();
-    if (e != hipSuccess) return e;
-    LargeParams p{};
+    g.step_lds = kLargeStepFixedBytes + size_t(B) * size_t(L.D) * 4;
+    if (g.step_lds > kRrefMaxLds) return hipErrorInvalidValue;
+    p = LargeParams{};
     p.pieces = rp.pieces;
     p.obj_stride = rp.obj_stride;
     p.piece_stride = rp.piece_stride;
@@ -522,7 +606,7 @@ hipError_t launch_rank_large(const RrefParams &rp, void *ws, size_t ws_bytes, hi
     p.T_obj = rp.T_obj;
     p.status = rp.status;
     p.rank = rp.rank;
-    p.ws = static_cast<uint32_t *>(ws);
+    p.ws = static_cast<uint32_t *>(const_cast<void *>(ws));
     p.ws_obj = int64_t(L.total);
     p.k = rp.k;
     p.m = rp.m;
@@ -532,15 +616,78 @@ hipError_t launch_rank_large(const RrefParams &rp, void *ws, size_t ws_bytes, hi
     const int64_t nobj = rp.n_obj;
     const int64_t g_reduce = nobj * p.chunks, g_update = g_reduce * p.row_chunks, g_final = nobj * p.fin_chunks;
     if (g_update > 0x7FFFFFFF || g_final > 0x7FFFFFFF) return hipErrorInvalidValue;
+    g.reduce = unsigned(g_reduce);
+    g.step = unsigned(nobj);
+    g.update = unsigned(g_update);
+    g.fin = unsigned(g_final);
+    return step_attr();
+}
+
+}  // namespace
+
+hipError_t launch_rank_large(const RrefParams &rp, void *ws, size_t ws_bytes, hipStream_t s) {
+    if (rp.n_obj <= 0) return hipSuccess;
+    LargeParams p;
+    LargeGrids g;
+    hipError_t e = large_setup(rp, ws, ws_bytes, p, g);
+    if (e != hipSuccess) return e;
+    const int B = large_block(rp.k, rp.m);
     for (int t0 = 0; t0 < rp.m; t0 += B) {
         p.t0 = t0;
         p.b = rp.m - t0 < B ? rp.m - t0 : B;
-        hipLaunchKernelGGL(gf_rank_large_reduce, dim3(unsigned(g_reduce)), dim3(256), 0, s, p);
-        hipLaunchKernelGGL(gf_rank_large_step, dim3(unsigned(nobj)), dim3(256), step_lds, s, p);
-        hipLaunchKernelGGL(gf_rank_large_update, dim3(unsigned(g_update)), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(gf_rank_large_reduce<false>, dim3(g.reduce), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(gf_rank_large_step<false>, dim3(g.step), dim3(256), g.step_lds, s, p);
+        hipLaunchKernelGGL(gf_rank_large_update, dim3(g.update), dim3(256), 0, s, p);
         if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(gf_rank_large_final, dim3(unsigned(g_final)), dim3(256), 0, s, p);
+    hipLaunchKernelGGL(gf_rank_large_final<false>, dim3(g.fin), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+hipError_t launch_rank_stream_init(int k, int m, int n_obj, void *state, size_t state_bytes, hipStream_t s) {
+    if (n_obj <= 0) return hipSuccess;
+    RrefParams rp{};
+    rp.k = k;
+    rp.m = m;
+    rp.n_obj = n_obj;
+    LargeParams p;
+    LargeGrids g;
+    hipError_t e = large_setup(rp, state, state_bytes, p, g);  // the grids of every later launch fit
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gf_rank_stream_init, dim3((unsigned(n_obj) + 255) / 256), dim3(256), 0, s, p.ws, p.ws_obj, n_obj);
+    return hipGetLastError();
+}
+
+hipError_t launch_rank_stream_push(const RrefParams &rp, void *state, size_t state_bytes, const int32_t *avail,
+                                   int max_new, int32_t *rank, int32_t *answered, hipStream_t s) {
+    if (rp.n_obj <= 0 || max_new <= 0) return hipSuccess;
+    if (avail == nullptr || rp.pieces == nullptr) return hipErrorInvalidValue;
+    LargeParams p;
+    LargeGrids g;
+    hipError_t e = large_setup(rp, state, state_bytes, p, g);
+    if (e != hipSuccess) return e;
+    const int B = large_block(rp.k, rp.m);
+    const int most = max_new < rp.m ? max_new : rp.m;
+    const dim3 per_obj((unsigned(rp.n_obj) + 255) / 256);
+    hipLaunchKernelGGL(gf_rank_stream_latch, per_obj, dim3(256), 0, s, p.ws, p.ws_obj, rp.n_obj, avail, rp.m, most);
+    for (int t = 0; t < most; t += B) {  // every block: each object's own next pieces, from its state
+        hipLaunchKernelGGL(gf_rank_large_reduce<true>, dim3(g.reduce), dim3(256), 0, s, p);
+        hipLaunchKernelGGL(gf_rank_large_step<true>, dim3(g.step), dim3(256), g.step_lds, s, p);
+        hipLaunchKernelGGL(gf_rank_large_update, dim3(g.update), dim3(256), 0, s, p);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    if (rank != nullptr || answered != nullptr)
+        hipLaunchKernelGGL(gf_rank_stream_progress, per_obj, dim3(256), 0, s, p.ws, p.ws_obj, rp.n_obj, rank, answered);
+    return hipGetLastError();
+}
+
+hipError_t launch_rank_stream_snapshot(const RrefParams &rp, const void *state, size_t state_bytes, hipStream_t s) {
+    if (rp.n_obj <= 0 || (rp.T == nullptr && rp.status == nullptr && rp.rank == nullptr)) return hipSuccess;
+    LargeParams p;
+    LargeGrids g;
+    hipError_t e = large_setup(rp, state, state_bytes, p, g);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gf_rank_large_final<true>, dim3(g.fin), dim3(256), 0, s, p);
     return hipGetLastError();
 }
 

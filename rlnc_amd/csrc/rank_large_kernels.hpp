@@ -66,4 +66,23 @@ inline size_t rank_large_workspace_bytes(size_t k, size_t m, size_t nobj) {
 // hipErrorInvalidValue for a shape outside the limits, a ragged table or a short workspace.
 hipError_t launch_rank_large(const RrefParams &p, void *ws, size_t ws_bytes, hipStream_t s);
 
+// ---- Decode streams (include/rlnc_hip.h, rlnc_decode_stream_*): the same state kept by the caller between calls ----
+// The state buffer has the workspace's layout; its fourth state word, spare in the one-shot form, holds the target of
+// the push in flight (pieces answered after it).  A push is one latch launch (target = min(max(avail, done), m, done +
+// max_new) per object), ceil(min(max_new, m) / B) blocks of the same three launches in their stream form -- each
+// object's block is pieces done .. min(done + B, target) - 1, read from its state; an object with nothing left returns
+// at once -- and, when asked for, one launch that copies out every object's rank and done.  The state after a push is
+// the one-piece-at-a-time model's after the same pieces (rank_large.hip: the proof is per block and does not care
+// where a block starts), so it does not depend on how the pieces were split over pushes.
+inline size_t rank_stream_state_bytes(size_t k, size_t m, size_t nobj) { return rank_large_workspace_bytes(k, m, nobj); }
+// rank, answered and target of every object to 0 (one launch); hipErrorInvalidValue as launch_rank_large
+hipError_t launch_rank_stream_init(int k, int m, int n_obj, void *state, size_t state_bytes, hipStream_t s);
+// p: pieces, obj_stride, piece_stride, k, m, n_obj.  avail int32 [n_obj] is read by the latch launch only; rank /
+// answered int32 [n_obj], each optional.  No synchronisation, no workspace beside the state.
+hipError_t launch_rank_stream_push(const RrefParams &p, void *state, size_t state_bytes, const int32_t *avail,
+                                   int max_new, int32_t *rank, int32_t *answered, hipStream_t s);
+// p: k, m, n_obj, T, T_obj, status, rank (each output optional): launch_rank_large's last launch on the stream's
+// state, RLNC_STATUS_PENDING for the slots not yet answered.  The state is only read.
+hipError_t launch_rank_stream_snapshot(const RrefParams &p, const void *state, size_t state_bytes, hipStream_t s);
+
 }  // namespace rlnc

@@ -33,6 +33,8 @@ pub const RLNC_RANK_MODE_TRUE: c_int = 1;
 // decode paths of rank mode 1 for every shape (rlnc_set_decode_path)
 pub const RLNC_DECODE_PATH_DEVICE_ANY: c_int = 7;
 pub const RLNC_DECODE_PATH_LARGE: c_int = 8;
+// a decode stream's slot that no push has answered yet (rlnc_decode_stream_snapshot)
+pub const RLNC_STATUS_PENDING: c_int = -1;
 
 // ---- opaque handles ----
 #[repr(C)]
@@ -479,6 +481,43 @@ unsafe extern "C" {
         object_status_dev: *mut i32,
         data_len_dev: *mut i64,
         plan_dev: *const c_void,
+    ) -> c_int;
+
+    // decode streams: the true-rank decoder state kept on the device between calls
+    pub fn rlnc_decode_stream_state_bytes(k: usize, m: usize, num_objects: usize) -> usize;
+    pub fn rlnc_decode_stream_init(
+        ctx: *mut rlnc_context,
+        state_dev: *mut c_void,
+        state_bytes: usize,
+        k: usize,
+        m: usize,
+        num_objects: usize,
+    ) -> c_int;
+    pub fn rlnc_decode_stream_push(
+        ctx: *mut rlnc_context,
+        state_dev: *mut c_void,
+        state_bytes: usize,
+        pieces_dev: *const u8,
+        pieces_obj_stride: usize,
+        k: usize,
+        L: usize,
+        m: usize,
+        num_objects: usize,
+        avail_dev: *const i32,
+        max_new: usize,
+        rank_dev: *mut i32,
+        answered_dev: *mut i32,
+    ) -> c_int;
+    pub fn rlnc_decode_stream_snapshot(
+        ctx: *mut rlnc_context,
+        state_dev: *const c_void,
+        state_bytes: usize,
+        k: usize,
+        m: usize,
+        num_objects: usize,
+        T_dev: *mut u8,
+        piece_status_dev: *mut i32,
+        rank_dev: *mut i32,
     ) -> c_int;
 
     // wire formats on the device
