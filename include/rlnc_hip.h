@@ -213,8 +213,8 @@ int rlnc_set_kernel_variant(rlnc_context *ctx, int variant, int max_tile_rows);
 int rlnc_set_column_run(rlnc_context *ctx, int col_run);
 /* Where rlnc_decode_batch runs the coefficient elimination: 0 = auto (device when it fits LDS, default),
  * 1 = host threads, 2 = device, 5 = device, blocked clean run (k + m <= 256, else RLNC_ERR_INVALID_ARGUMENT; what 0
- * and 2 use when it applies).  The A/B build adds 3 (clean state on LDS), 4 (one wave's registers) and 6 (the
- * round-1 multi-wave register path).  All of these are exact replicas; the switch exists for A/B tests.
+ * and 2 use when it applies).  All of these are exact replicas; the switch exists for A/B tests.  Every other value
+ * is RLNC_ERR_INVALID_ARGUMENT and leaves the path as it was (3, 4 and 6 once named forms that are retired).
  * Rank mode 1 only (in mode 0 every decode call under them returns RLNC_ERR_INVALID_ARGUMENT, no silent fallback):
  * RLNC_DECODE_PATH_DEVICE_ANY (7) = the device for every shape -- the LDS kernel where it fits, beyond that the
  * workspace-resident true-rank kernels (rlnc_amd/csrc/rank_large.hip), so rlnc_decode_batch makes no host round trip
@@ -231,9 +231,8 @@ size_t rlnc_decode_large_workspace_bytes(size_t k, size_t m, size_t num_objects)
 /* Rank mode of the context (see "Rank mode" above): governs rlnc_decode_batch, rlnc_decode_batch_device,
  * rlnc_decode_batch_eliminate, rlnc_decode_ragged and rlnc_decode_host_stream, and is snapshotted by rlnc_decoder_new.
  * Other values: RLNC_ERR_INVALID_ARGUMENT.  In mode 1 decode paths 0 and 2 use the true-rank device kernel when it
- * fits, path 1 the host, paths 7 and 8 the device for every shape (rlnc_set_decode_path); path 5 (and the A/B build's
- * 3, 4, 6) name reference-mode kernels and make the decode calls return RLNC_ERR_INVALID_ARGUMENT (no silent
- * fallback). */
+ * fits, path 1 the host, paths 7 and 8 the device for every shape (rlnc_set_decode_path); path 5 names a
+ * reference-mode kernel and makes the decode calls return RLNC_ERR_INVALID_ARGUMENT (no silent fallback). */
 #define RLNC_RANK_MODE_REFERENCE 0
 #define RLNC_RANK_MODE_TRUE 1
 int rlnc_set_rank_mode(rlnc_context *ctx, int mode);

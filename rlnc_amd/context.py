@@ -49,9 +49,8 @@ class Context:
 
     def set_decode_path(self, path: int = 0):
         """0 auto, 1 host elimination, 2 device elimination, 5 device blocked clean run (what 0/2 use when
-        k + m <= 256; InvalidArgument when it does not apply).  The diagnostic A/B build (make -C rlnc_amd/csrc ab)
-        adds 3 (clean state on LDS), 4 (one wave's registers) and 6 (the round-1 multi-wave register path).  All
-        are exact.  Rank mode 1 only (InvalidArgument from every decode call in mode 0): 7
+        k + m <= 256; InvalidArgument when it does not apply).  All are exact; every other value is InvalidArgument
+        and leaves the path as it was.  Rank mode 1 only (InvalidArgument from every decode call in mode 0): 7
         (RLNC_DECODE_PATH_DEVICE_ANY) the device for every shape -- the LDS kernel where it fits, the workspace-resident
         true-rank kernels beyond (k <= 4096, m <= 8192), so decode_batch_device / decode_batch_eliminate accept such
         shapes and decode_batch / decode_ragged / decode_host_stream make no host round trip for the elimination; 8
@@ -63,7 +62,7 @@ class Context:
         sparse or structured coding vectors included).  1: true rank -- a piece is useful exactly when it is linearly
         independent of the useful pieces before it (not the crate's behaviour on such input).  Governs this context's
         decode_batch / decode_batch_device / decode_batch_eliminate / decode_ragged / decode_host_stream calls and
-        the decoders created on it afterwards.  In mode 1 decode paths 3-6 are InvalidArgument, in mode 0 paths 7 and 8."""
+        the decoders created on it afterwards.  In mode 1 decode path 5 is InvalidArgument, in mode 0 paths 7 and 8."""
         check(self.lib.rlnc_set_rank_mode(self.h, int(mode)), self.lib)
 
     @property

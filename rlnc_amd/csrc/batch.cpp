@@ -166,7 +166,7 @@ int decode_eliminate_impl(rlnc_context *ctx, const uint8_t *pieces, size_t obj_s
         return RLNC_OK;
     }
     if (int st = ctx->rank_mode_path_check()) return st;  // paths 7 and 8 in mode 0
-    rp.lds_only = ctx->decode_path == 3 ? 1 : ctx->decode_path == 4 ? 2 : ctx->decode_path == 5 ? 3 : ctx->decode_path == 6 ? 4 : 0;
+    rp.block_only = ctx->decode_path == 5 ? 1 : 0;
     if (ctx->decode_path == 5 && !rlnc::rref_block_eligible(int(k), int(m)))  // no silent fallback to another kernel
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "decode path 5 (blocked run) needs k + m <= 256 (k=%zu, m=%zu)", k, m);
     rp.bsj_stream = bsj;

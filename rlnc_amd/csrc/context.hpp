@@ -243,10 +243,8 @@ struct rlnc_context {
     int max_tile_rows = 0;
     int col_run = 0;  // column blocks per workgroup of variant 9 (0 = chosen per launch; rlnc_set_column_run)
     int decode_path = 0;  // 0 auto (device when it fits LDS), 1 host elimination, 2 device elimination,
-                          // 3 device elimination with the clean state on LDS, 4 ... on one wave's
-                          // registers, 5 blocked clean run, 6 round-1 multi-wave registers (A/B),
-                          // 7 device for every shape (rank mode 1: rank.hip where it fits LDS, rank_large.hip
-                          // beyond), 8 rank_large.hip for every shape
+                          // 5 blocked clean run, 7 device for every shape (rank mode 1: rank.hip where it fits LDS,
+                          // rank_large.hip beyond), 8 rank_large.hip for every shape (3, 4, 6: retired, never set)
     int rank_mode = 0;  // RLNC_RANK_MODE_*: 0 the reference's diagonal-pivot replica, 1 true rank (rank.hip, elimination.hpp)
     // the device elimination of this context's rank mode fits LDS
     bool elim_fits(size_t k, size_t m) const {
@@ -260,7 +258,7 @@ struct rlnc_context {
     }
     // the elimination of this shape can run on the device
     bool elim_on_device(size_t k, size_t m) const { return elim_fits(k, m) || elim_large(k, m); }
-    // decode paths 3-6 name reference-mode kernels, 7 and 8 true-rank kernels: no silent fallback in the other mode
+    // decode path 5 names a reference-mode kernel, 7 and 8 true-rank kernels: no silent fallback in the other mode
     int rank_mode_path_check() const {
         const bool large = decode_path == RLNC_DECODE_PATH_DEVICE_ANY || decode_path == RLNC_DECODE_PATH_LARGE;
         if (rank_mode == RLNC_RANK_MODE_TRUE && decode_path >= 3 && !large)

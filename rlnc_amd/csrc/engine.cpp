@@ -133,13 +133,11 @@ int rlnc_context_synchronize(rlnc_context *ctx) {
     return RLNC_OK;
 }
 
-// Shipped decode paths: 0 auto, 1 host, 2 device, 5 device blocked run, 7 and 8 the true-rank kernels for every shape
-// (rank mode 1); 3, 4 and 6 (the round-1 LDS / register forms) exist in the diagnostic build only (make -C
-// rlnc_amd/csrc ab: rref_ab.hip).
+// Decode paths: 0 auto, 1 host, 2 device, 5 device blocked run, 7 and 8 the true-rank kernels for every shape (rank
+// mode 1).  3, 4 and 6 were the round-1 LDS / register forms, retired: invalid in every build.
 int rlnc_set_decode_path(rlnc_context *ctx, int path) {
     CHECK_ARG(ctx != nullptr && (path == 0 || path == 1 || path == 2 || path == 5 ||
-                                 path == RLNC_DECODE_PATH_DEVICE_ANY || path == RLNC_DECODE_PATH_LARGE ||
-                                 (rlnc::ab_build() && (path == 3 || path == 4 || path == 6))));
+                                 path == RLNC_DECODE_PATH_DEVICE_ANY || path == RLNC_DECODE_PATH_LARGE));
     ctx->decode_path = path;
     return RLNC_OK;
 }

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
+#include <mutex>
 
 namespace rlnc {
 
@@ -77,11 +78,10 @@ hipError_t launch_matmul(const MatmulParams &p, hipStream_t stream, MatmulVarian
 
 struct RrefParams;
 
-// ---- the A/B build (make ab: kernels_ab.hip adds matmul variants 2-5 and 9, rref_ab.hip decode paths 3, 4, 6) ----
+// ---- the A/B build (make ab: kernels_ab.hip adds matmul variants 2-5 and 9) ----
 // The shipped library defines these weakly (ab_build() false, the launches hipErrorInvalidValue); the A/B build's
 // definitions replace them.
 bool ab_build();
-bool launch_rref_ab(const RrefParams &p, hipStream_t s, hipError_t *result);  // true: launched (*result its status)
 hipError_t launch_matmul_ab(const MatmulParams &p, hipStream_t s, MatmulVariant v, void *scratch, size_t scratch_bytes);
 size_t matmul_scratch_bytes_ab(const MatmulParams &p, MatmulVariant v);
 // what the A/B variants reuse of the shipped bit-sliced jump path (kernels.hip): eligibility (whole 4 KiB column blocks
@@ -166,8 +166,8 @@ struct RrefParams {
     int64_t T_obj;
     int32_t *status;
     int32_t *rank;
-    int lds_only;  // clean-state path (A/B, all exact): 0 auto (blocked clean run when k + m <= 256, else 4);
-                   // 1 LDS; 2 registers, one wave; 3 blocked clean run (gf_rref_block_kernel); 4 registers, multi-wave
+    int block_only;  // 1 = decode path 5: the blocked run (gf_rref_block_kernel), never the small-object kernel or the
+                     // two-pass split; 0 = chosen by shape (launch_rref_one)
     const struct RrefObj *objs = nullptr;  // ragged batch: object o's shape and buffers (the fields above unused)
     // two-pass elimination when k + m > 256 (k <= 128): pass 1 (the blocked run) replays only the first m pieces of
     // each object with statuses / T at row stride m_stride (> m): an object full-ranked within them is exact
@@ -190,8 +190,6 @@ struct RrefParams {
     int64_t *tail_len = nullptr;
     int32_t *tail_need = nullptr;
     int64_t tail_L = 0;
-    // diagnostic build only (rref_ab.hip, RLNC_SMALL_PROF): per-wave phase timestamps of the small-object kernel
-    uint64_t *prof = nullptr;
 };
 // One object of a ragged elimination launch (rlnc_decode_ragged): T is k x m row-major, status m entries.
 struct RrefObj {
@@ -210,6 +208,27 @@ size_t rref_block_lds_bytes_public(int k, int m);
 hipError_t launch_rref_ragged(const RrefObj *objs, int n, bool block, size_t lds, int hdr_lds, hipStream_t s);
 size_t rref_lds_bytes_staged_public(int k, int m);
 constexpr size_t kRrefMaxLds = 160 * 1024;
+// hipFuncAttributeMaxDynamicSharedMemorySize = kRrefMaxLds for a call site's kernels, set once per device (function
+// attributes are per device) under a lock: one static instance per call site, set() before the launch
+struct MaxLdsAttr {
+    std::mutex mu;
+    bool done[64] = {};
+    template <class... Kernels>
+    hipError_t set(Kernels... kernels) {
+        int dev = 0;
+        hipError_t e = hipGetDevice(&dev);
+        if (e != hipSuccess) return e;
+        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
+        std::lock_guard<std::mutex> lock(mu);
+        if (done[dev]) return hipSuccess;
+        for (const void *f : {reinterpret_cast<const void *>(kernels)...}) {
+            e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
+            if (e != hipSuccess) return e;
+        }
+        done[dev] = true;
+        return hipSuccess;
+    }
+};
 size_t rref_lds_bytes(int k, int m);
 // the blocked clean-run kernel (decode path 5, and what 0 / 2 pick) applies: a row fits one wave (k + m <= 256)
 bool rref_block_eligible(int k, int m);

@@ -17,18 +17,10 @@
 // objects per workgroup over one table copy; a wave's LDS operations execute in issue order, so a fence suffices).
 // Every branch around a barrier depends on values all the threads of the object read from LDS after the previous
 // barrier (rank, pc), taken through readfirstlane.
-#include <mutex>
-
 #include "../../include/rlnc_hip.h"
+#include "gf_perm.hpp"
 #include "kernels.hpp"
 #include "rank_kernels.hpp"
-// the helpers of the reference-mode kernels (the v_perm GF table, mul4, gfinv, ballot, rsync); the kernels themselves
-// are not used here
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#include "rref_kernels.hpp"
-#pragma clang diagnostic pop
 
 namespace rlnc {
 
@@ -78,13 +70,7 @@ __global__ __launch_bounds__(256) void gf_true_rank_kernel(RrefParams p) {
     int32_t *ord = piv + k;
     uint8_t *qb = reinterpret_cast<uint8_t *>(ord + k);
 
-    {  // the table copy: both loads in flight at once
-        const uint4 *src = reinterpret_cast<const uint4 *>(kRrefTable.v);
-        uint4 *dst = reinterpret_cast<uint4 *>(tab);
-        const uint4 a = src[threadIdx.x], b = src[threadIdx.x + 256];
-        dst[threadIdx.x] = a;
-        dst[threadIdx.x + 256] = b;
-    }
+    copy_table(tab);
     if (valid) {  // all m headers, 8 independent byte loads in flight per batch
         const uint8_t *base = p.pieces + int64_t(o) * p.obj_stride;
         uint8_t *hdst = reinterpret_cast<uint8_t *>(Hw);
@@ -158,7 +144,7 @@ __global__ __launch_bounds__(256) void gf_true_rank_kernel(RrefParams p) {
             }
         }
         pc = __builtin_amdgcn_readfirstlane(pc);
-        val = uint32_t(__builtin_amdgcn_readfirstlane(int(val)));
+        val = uni(val);
         if (pc < 0) {
             if (tid == 0) St[pi] = RLNC_ERR_PIECE_NOT_USEFUL;
             par ^= 1;
@@ -213,20 +199,8 @@ __global__ __launch_bounds__(256) void gf_true_rank_kernel(RrefParams p) {
 
 // the 160 KiB dynamic-LDS attribute of the workgroup form, once per device
 hipError_t rank_attr() {
-    static std::mutex mu;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_true_rank_kernel<256>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    return hipSuccess;
+    static MaxLdsAttr attr;
+    return attr.set(&gf_true_rank_kernel<256>);
 }
 
 }  // namespace

@@ -5,7 +5,7 @@
 // reduced row-echelon form with free pivot columns, so a piece is useful exactly when it is linearly independent of
 // the useful pieces before it (include/rlnc_hip.h, "Rank mode").  It reads k, m, n_obj, pieces, the strides, T,
 // T_obj, status, rank and objs of RrefParams; it writes neither bsj_stream nor the tail_* outputs and ignores
-// lds_only, m_stride, skip_full (RrefObj: m_first, two_pass).
+// block_only, m_stride, skip_full (RrefObj: m_first, two_pass).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -41,19 +41,12 @@
 // Rules kept by every kernel: no workgroup waits for another; every branch around a barrier is workgroup-uniform, on
 // values read after the previous barrier and passed through readfirstlane; the early return (nothing left to do) comes
 // before any barrier; shared global state is ordered by barriers and kernel boundaries only.
-#include <mutex>
 #include <type_traits>
 
 #include "../../include/rlnc_hip.h"
+#include "gf_perm.hpp"
 #include "kernels.hpp"
 #include "rank_large_kernels.hpp"
-// the helpers of the reference-mode kernels (the v_perm GF table, mul4, gfinv, ballot); the kernels themselves are not
-// used here
-#pragma clang diagnostic push
-#pragma clang diagnostic ignored "-Wunused-function"
-#pragma clang diagnostic ignored "-Wunneeded-internal-declaration"
-#include "rref_kernels.hpp"
-#pragma clang diagnostic pop
 
 namespace rlnc {
 
@@ -80,17 +73,6 @@ struct LargeParams {
     // fastest, then the update's row chunks / the final launch's row chunks, then objects
     int chunks, row_chunks, fin_chunks;
 };
-
-// both halves of the 8 KiB table copy in flight at once (256 threads)
-__device__ __forceinline__ void copy_table(uint32_t *tab) {
-    const uint4 *src = reinterpret_cast<const uint4 *>(kRrefTable.v);
-    uint4 *dst = reinterpret_cast<uint4 *>(tab);
-    const uint4 a = src[threadIdx.x], b = src[threadIdx.x + 256];
-    dst[threadIdx.x] = a;
-    dst[threadIdx.x + 256] = b;
-}
-
-__device__ __forceinline__ uint32_t uni(uint32_t v) { return uint32_t(__builtin_amdgcn_readfirstlane(int(v))); }
 
 // The stream form of a block (STREAM kernels; rank_large_kernels.hpp, "Decode streams"): the object's own block, from
 // its state instead of the launch's t0 and b -- pieces done .. min(done + B, target) - 1, where the push's latch launch
@@ -565,23 +547,8 @@ __global__ __launch_bounds__(256) void gf_rank_stream_progress(const uint32_t *w
 
 // the 160 KiB dynamic-LDS attribute of the block step (both forms), once per device
 hipError_t step_attr() {
-    static std::mutex mu;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!attr_set[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_rank_large_step<false>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
-        if (e != hipSuccess) return e;
-        e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_rank_large_step<true>),
-                                hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
-        if (e != hipSuccess) return e;
-        attr_set[dev] = true;
-    }
-    return hipSuccess;
+    static MaxLdsAttr attr;
+    return attr.set(&gf_rank_large_step<false>, &gf_rank_large_step<true>);
 }
 
 // the launches' common part: the shape and workspace checks, the step's LDS attribute, the parameters and the grids

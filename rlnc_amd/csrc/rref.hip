@@ -23,11 +23,7 @@
 // then never waits on HBM.
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-#include <mutex>
-
 #include "../../include/rlnc_hip.h"
-#include "gf256.hpp"
 #include "kernels.hpp"
 #include "rref_kernels.hpp"
 
@@ -42,10 +38,13 @@ size_t rref_lds_bytes(int k, int m) {
 }
 
 size_t rref_block_lds_bytes_public(int k, int m) { return rref_block_lds_bytes(k, m); }
-
-// The A/B build (make ab) links rref_ab.hip, whose definition replaces this one
-__attribute__((weak)) bool launch_rref_ab(const RrefParams &, hipStream_t, hipError_t *) { return false; }
 size_t rref_lds_bytes_staged_public(int k, int m) { return rref_lds_bytes_staged(k, m); }
+
+// the 160 KiB dynamic-LDS attribute of the two kernels launched with more than the default limit
+static hipError_t rref_lds_attr() {
+    static MaxLdsAttr attr;
+    return attr.set(&gf_rref_block_kernel<kBlkNW, kBlkB>, &gf_rref_batch_kernel);
+}
 
 hipError_t launch_rref_ragged(const RrefObj *objs, int n, bool block, size_t lds, int hdr_lds, hipStream_t s) {
     if (n <= 0) return hipSuccess;
@@ -54,29 +53,12 @@ hipError_t launch_rref_ragged(const RrefObj *objs, int n, bool block, size_t lds
     p.objs = objs;
     p.n_obj = n;
     p.skip_full = block ? 0 : 1;  // the general launch skips two-pass objects the blocked launch full-ranked
-    // the dynamic-LDS attribute of both kernels (a first launch through launch_rref_batch may not have run yet)
-    static std::mutex mu;
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    const hipError_t e = rref_lds_attr();
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_rref_block_kernel<kBlkNW, 8>),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
-            if (e == hipSuccess)
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(&gf_rref_batch_kernel<0, 1, 1>),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
-            if (e != hipSuccess) return e;
-            attr_set[dev] = true;
-        }
-    }
     if (block)
-        hipLaunchKernelGGL((gf_rref_block_kernel<kBlkNW, 8>), dim3(n), dim3(64 * kBlkNW), lds, s, p);
+        hipLaunchKernelGGL((gf_rref_block_kernel<kBlkNW, kBlkB>), dim3(n), dim3(64 * kBlkNW), lds, s, p);
     else
-        hipLaunchKernelGGL((gf_rref_batch_kernel<0, 1, 1>), dim3(n), dim3(64), lds, s, p, hdr_lds);
+        hipLaunchKernelGGL(gf_rref_batch_kernel, dim3(n), dim3(64), lds, s, p, hdr_lds);
     return hipGetLastError();
 }
 
@@ -88,7 +70,7 @@ static hipError_t launch_rref_one(const RrefParams &p, hipStream_t s, bool *bsj_
 hipError_t launch_rref_batch(const RrefParams &p, hipStream_t s, bool *bsj_written) {
     if (bsj_written) *bsj_written = false;
     if (p.n_obj <= 0) return hipSuccess;
-    if (p.lds_only == 0 && p.objs == nullptr && p.m_stride == 0 && !p.skip_full && p.k <= 128 &&
+    if (!p.block_only && p.objs == nullptr && p.m_stride == 0 && !p.skip_full && p.k <= 128 &&
         rref_row_dwords(p.k, p.m) > 64 && rref_lds_bytes(p.k, p.m) <= kRrefMaxLds &&
         rref_block_lds_bytes(p.k, 256 - p.k) <= kRrefMaxLds) {
         RrefParams a = p;
@@ -107,51 +89,25 @@ hipError_t launch_rref_batch(const RrefParams &p, hipStream_t s, bool *bsj_writt
     return launch_rref_one(p, s, bsj_written);
 }
 
+// One launch, one of three kernels by shape: the small-object kernel (two shapes), the blocked run, the one-wave LDS
+// kernel (headers staged in LDS or not).
 static hipError_t launch_rref_one(const RrefParams &p, hipStream_t s, bool *bsj_written) {
-    hipError_t ab = hipSuccess;
-    if (launch_rref_ab(p, s, &ab)) return ab;  // the A/B build's paths (rref_ab.hip); false in the shipped library
-    // many small objects (k <= 16, >= 2048 of them: 8 per CU and more): the one-wave register kernel (path 4's)
-    // beats the 4-wave blocked run, whose per-object parallelism the full grid no longer needs -- 4,096 x k = 16:
-    // 0.093 vs 0.125 ms, k = 8: 0.051 vs 0.067, k = 16 sparse + dependent: 0.195 vs 0.295; at 512 objects the
-    // blocked run stays faster (0.035 vs 0.049) (profiles/r02_elim_small_k.jsonl)
-    constexpr int small_min = kSmallMinObjects;
-    const bool small_many = p.lds_only == 0 && p.k <= 16 && p.n_obj >= small_min && rref_row_dwords(p.k, p.m) <= 16 &&
-                            rref_lds_bytes_staged(p.k, p.m) <= kRrefMaxLds;
-    // the blocked clean run (4 waves per object, the default) when the row fits one wave (k + m <= 256)
-    if (!small_many && (p.lds_only == 0 || p.lds_only == 3) && rref_row_dwords(p.k, p.m) <= 64 &&
-        rref_block_lds_bytes(p.k, p.m) <= kRrefMaxLds) {
-        static_assert(kBlkDefault == 8, "the shipped block size");
-        auto kern = &gf_rref_block_kernel<kBlkNW, 8>;
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        {
-            std::lock_guard<std::mutex> lock(mu);
-            if (!attr_set[dev]) {
-                for (auto f : {&gf_rref_block_kernel<kBlkNW, 8>}) {
-                    e = hipFuncSetAttribute(reinterpret_cast<const void *>(f), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                            int(kRrefMaxLds));
-                    if (e != hipSuccess) return e;
-                }
-                attr_set[dev] = true;
-            }
-        }
-        hipLaunchKernelGGL(kern, dim3(p.n_obj), dim3(64 * kBlkNW), rref_block_lds_bytes(p.k, p.m), s, p);
-        return hipGetLastError();
-    }
-    if (small_many && p.k <= 16 && rref_row_dwords(p.k, p.m) <= 16) {
+    const int D = rref_row_dwords(p.k, p.m);
+    // many small objects (k <= 16, >= 2048 of them: 8 per CU and more): the one-wave register kernel beats the 4-wave
+    // blocked run, whose per-object parallelism the full grid no longer needs -- 4,096 x k = 16: 0.093 vs 0.125 ms,
+    // k = 8: 0.051 vs 0.067, k = 16 sparse + dependent: 0.195 vs 0.295; at 512 objects the blocked run stays faster
+    // (0.035 vs 0.049) (profiles/r02_elim_small_k.jsonl)
+    if (!p.block_only && p.k <= 16 && p.n_obj >= kSmallMinObjects && D <= 16 &&
+        rref_lds_bytes_staged(p.k, p.m) <= kRrefMaxLds) {
         // kSmallNW objects per workgroup over one table copy (<= 16 KiB + 4 x 2 KiB: under the default LDS limit)
         // rows of 8 dwords or fewer (k + m <= 32): 8 lane groups of 4 registers (123 VGPRs: 4 waves per SIMD) and
         // kSmallNW objects per workgroup; wider rows: 4 groups of 8 (199 VGPRs, 2 waves per SIMD, where the 8 objects
         // per CU the one-object workgroups already hold are all the VGPRs allow) -- profiles/r03_small_elim_ab.txt
         // rows <= k <= 16 = G x RT: 2 registers of 8 lane groups (4 of 4 groups) hold every row; the round-4 forms
         // carried 4 (8) registers per lane, half of them always zero rows (products with q = 0, still issued)
-        const bool g8 = rref_row_dwords(p.k, p.m) <= 8;
+        const bool g8 = D <= 8;
         auto kern = g8 ? &gf_rref_small_kernel<kSmallNW, 8, 2> : &gf_rref_small_kernel<1, 4, 4>;
-        int nw = g8 ? kSmallNW : 1;
+        const int nw = g8 ? kSmallNW : 1;
         const size_t lds_small = size_t(kTabEntries) * kTabDw * 4 + nw * rref_small_wave_bytes(p.k, p.m) +
                                  (p.tail_status != nullptr ? nw * rref_small_tail_bytes(p.m) : 0);
         hipLaunchKernelGGL(kern, dim3((p.n_obj + nw - 1) / nw), dim3(64 * nw), lds_small, s, p);
@@ -159,38 +115,22 @@ static hipError_t launch_rref_one(const RrefParams &p, hipStream_t s, bool *bsj_
         if (e == hipSuccess && bsj_written) *bsj_written = p.bsj_stream != nullptr && p.bsj_tile_rows > 0;
         return e;
     }
+    // the blocked clean run (4 waves per object) when the row fits one wave (k + m <= 256)
+    if (D <= 64 && rref_block_lds_bytes(p.k, p.m) <= kRrefMaxLds) {
+        const hipError_t e = rref_lds_attr();
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL((gf_rref_block_kernel<kBlkNW, kBlkB>), dim3(p.n_obj), dim3(64 * kBlkNW),
+                           rref_block_lds_bytes(p.k, p.m), s, p);
+        return hipGetLastError();
+    }
+    // else the one-wave LDS kernel, with all headers staged in LDS when they fit beside the matrix
     size_t lds = rref_lds_bytes(p.k, p.m);
-    if (lds > kRrefMaxLds) return hipErrorInvalidValue;
+    if (lds > kRrefMaxLds || p.block_only) return hipErrorInvalidValue;
     const int hdr_lds = rref_lds_bytes_staged(p.k, p.m) <= kRrefMaxLds ? 1 : 0;
     if (hdr_lds) lds = rref_lds_bytes_staged(p.k, p.m);
-    // register-resident clean path when the matrix fits: rows <= G·RT, row dwords <= 64 / G; the initial clean
-    // run spread over 4 waves (reg_run_mw) up to k = 64
-    const int D = rref_row_dwords(p.k, p.m);
-    auto kern = &gf_rref_batch_kernel<0, 1, 1>;
-    int threads = 64;
-    // shipped paths: the blocked run above (k + m <= 256), the one-wave register kernel for many small objects,
-    // else the one-wave LDS kernel (the multi-wave register forms of decode paths 3/4/6 are diagnostic builds only)
-    if (p.lds_only != 0 || (small_many && !hdr_lds)) return hipErrorInvalidValue;
-    if (small_many && D <= 16 && p.k <= 32) kern = &gf_rref_batch_kernel<4, 8, 1>;
-    // the 160 KiB dynamic-LDS attribute, once per device (function attributes are per device), under a lock
-    {
-        static std::mutex mu;
-        static bool attr_set[64] = {};
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        std::lock_guard<std::mutex> lock(mu);
-        if (!attr_set[dev]) {
-            for (auto f : {&gf_rref_batch_kernel<0, 1, 1>, &gf_rref_batch_kernel<4, 8, 1>}) {
-                e = hipFuncSetAttribute(reinterpret_cast<const void *>(f),
-                                        hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
-                if (e != hipSuccess) return e;
-            }
-            attr_set[dev] = true;
-        }
-    }
-    hipLaunchKernelGGL(kern, dim3(p.n_obj), dim3(threads), lds, s, p, hdr_lds);
+    const hipError_t e = rref_lds_attr();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(gf_rref_batch_kernel, dim3(p.n_obj), dim3(64), lds, s, p, hdr_lds);
     return hipGetLastError();
 }
 

@@ -1,12 +1,10 @@
-// rref_kernels.hpp — the device elimination's kernels (see rref.hip for the algorithm), shared by the shipped
-// dispatch of rref.hip and the A/B dispatch of rref_ab.hip (internal to librlnc_hip).
+// rref_kernels.hpp — the device elimination's kernels (see rref.hip for the algorithm and the dispatch; internal to
+// librlnc_hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <cstdlib>
-
 #include "../../include/rlnc_hip.h"
-#include "gf256.hpp"
+#include "gf_perm.hpp"
 #include "kernels.hpp"
 
 namespace rlnc {
@@ -23,88 +21,6 @@ __host__ __device__ inline int rref_row_dwords(int k, int m) {
 
 namespace {
 
-constexpr int kTabDw = 8;  // dwords per multiplier: t0lo t0hi t1lo t1hi t2 inv - -
-
-// The 512 × kTabDw table, built at compile time: entry c < 256 = make_perm_table's layout of multiplier c plus
-// c^-1 = c^254 in dword 5; entry 256 + c = the layout of c^-1 (0 for c = 0), so that "multiply by the
-// inverse of the pivot" is one table read (the register path's normalisation).
-constexpr int kTabEntries = 512;
-struct RrefTable {
-    uint32_t v[kTabEntries * kTabDw];
-};
-constexpr void fill_perm_entry(uint32_t *e, uint8_t c) {
-    uint8_t m[8] = {};
-    m[0] = c;
-    for (int b = 1; b < 8; ++b) m[b] = gf_xtime(m[b - 1]);
-    uint32_t t0lo = 0, t0hi = 0, t1lo = 0, t1hi = 0, t2 = 0;
-    for (int x = 0; x < 8; ++x) {
-        uint8_t a = 0, h = 0;
-        for (int b = 0; b < 3; ++b)
-            if (x & (1 << b)) {
-                a = uint8_t(a ^ m[b]);
-                h = uint8_t(h ^ m[b + 3]);
-            }
-        if (x < 4) {
-            t0lo |= uint32_t(a) << (8 * x);
-            t1lo |= uint32_t(h) << (8 * x);
-        } else {
-            t0hi |= uint32_t(a) << (8 * (x - 4));
-            t1hi |= uint32_t(h) << (8 * (x - 4));
-        }
-    }
-    for (int x = 0; x < 4; ++x) {
-        uint8_t a = 0;
-        for (int b = 0; b < 2; ++b)
-            if (x & (1 << b)) a = uint8_t(a ^ m[b + 6]);
-        t2 |= uint32_t(a) << (8 * x);
-    }
-    e[0] = t0lo;
-    e[1] = t0hi;
-    e[2] = t1lo;
-    e[3] = t1hi;
-    e[4] = t2;
-}
-constexpr RrefTable build_rref_table() {
-    RrefTable t{};
-    // inverses by the generator-3 logarithm (gf256.rs:16-44, 88-108): c^-1 = 3^(255 - log3 c)
-    uint8_t ex[256] = {}, lg[256] = {};
-    uint8_t x = 1;
-    for (int i = 0; i < 255; ++i) {
-        ex[i] = x;
-        lg[x] = uint8_t(i);
-        x = uint8_t(x ^ gf_xtime(x));  // x·3
-    }
-    for (int c = 0; c < 256; ++c) {
-        const uint8_t inv = c ? ex[(255 - lg[c]) % 255] : uint8_t(0);
-        fill_perm_entry(t.v + c * kTabDw, uint8_t(c));
-        t.v[c * kTabDw + 5] = inv;
-        fill_perm_entry(t.v + (256 + c) * kTabDw, inv);
-    }
-    return t;
-}
-__device__ const RrefTable kRrefTable = build_rref_table();
-// spot checks against the field (gf256.rs:16-44): identity tables of c = 1, 2^-1 = 0x8D, 3^-1 = 0xF6
-static_assert(build_rref_table().v[1 * kTabDw + 0] == 0x03020100u && build_rref_table().v[1 * kTabDw + 1] == 0x07060504u,
-              "c = 1 low table");
-static_assert(build_rref_table().v[2 * kTabDw + 5] == 0x8Du && build_rref_table().v[3 * kTabDw + 5] == 0xF6u,
-              "inverses");
-static_assert(build_rref_table().v[(256 + 1) * kTabDw + 0] == 0x03020100u, "1^-1 = 1");
-
-__device__ __forceinline__ uint32_t mul4(const uint32_t *tab, uint32_t q, uint32_t x) {
-    const uint4 t = *reinterpret_cast<const uint4 *>(tab + q * kTabDw);
-    const uint32_t t2 = tab[q * kTabDw + 4];
-    return __builtin_amdgcn_perm(t.y, t.x, x & 0x07070707u) ^ __builtin_amdgcn_perm(t.w, t.z, (x >> 3) & 0x07070707u) ^
-           __builtin_amdgcn_perm(t2, t2, (x >> 6) & 0x03030303u);
-}
-__device__ __forceinline__ uint32_t mul4t(uint4 t, uint32_t t2, uint32_t x) {
-    return __builtin_amdgcn_perm(t.y, t.x, x & 0x07070707u) ^ __builtin_amdgcn_perm(t.w, t.z, (x >> 3) & 0x07070707u) ^
-           __builtin_amdgcn_perm(t2, t2, (x >> 6) & 0x03030303u);
-}
-__device__ __forceinline__ uint32_t gfmul(const uint32_t *tab, uint32_t a, uint32_t b) {
-    return mul4(tab, a, b) & 0xFFu;
-}
-__device__ __forceinline__ uint32_t gfinv(const uint32_t *tab, uint32_t a) { return tab[a * kTabDw + 5]; }
-
 // bytes of dword w at columns >= c0
 __device__ __forceinline__ uint32_t from_mask(int w, int c0) {
     const int b0 = 4 * w;
@@ -120,30 +36,11 @@ struct Mat {
     __device__ uint32_t at(int r, int c) const { return b[r * S + c]; }
 };
 
-// lane within the wave: the single-wave helpers below also run in one wave of a multi-object workgroup
-__device__ __forceinline__ int lane_id() { return int(threadIdx.x & 63u); }
-
 // row_t[c >= c0] ^= q · row_s[c >= c0]   (simd/mod.rs:89-119 on the byte range of decoder_matrix.rs:158-161)
 __device__ __forceinline__ void row_muladd(const Mat &M, const uint32_t *tab, int t, int s, uint32_t q, int c0) {
     for (int w = lane_id(); w < M.D; w += 64) {
         const uint32_t mask = from_mask(w, c0);
         if (mask) M.w[t * M.D + w] ^= mul4(tab, q, M.w[s * M.D + w]) & mask;
-    }
-}
-
-__device__ __forceinline__ uint64_t ballot(bool p) { return __ballot(p); }
-
-
-// WG: a workgroup barrier; else the code runs in one wave only (the other waves of the workgroup are elsewhere and
-// must not be waited for): a compiler fence suffices, a wave's LDS operations execute in issue order
-template <bool WG>
-__device__ __forceinline__ void rsync() {
-    if constexpr (WG) {
-        __syncthreads();
-    } else {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-        __builtin_amdgcn_wave_barrier();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     }
 }
 
@@ -429,7 +326,7 @@ __device__ int clean_append(const Mat &M, const uint32_t *tab, int r, int k, boo
 //   normalise from column r+1 (:200-211), byte r := 1;
 //   backward (:179-198) every row j < r ^= M[j][r]·row_r, M[j][r] broadcast from lane (r/4, g).
 // ---------------------------------------------------------------------------------------------------
-template <int G, int RT, bool WG = true>
+template <int G, int RT>
 __device__ void regs_to_lds(const Mat &M, const uint32_t (&v)[RT], int rows) {
     constexpr int DP = 64 / G;
     const int w = lane_id() % DP, g = lane_id() / DP;
@@ -438,7 +335,7 @@ __device__ void regs_to_lds(const Mat &M, const uint32_t (&v)[RT], int rows) {
         const int row = G * t + g;
         if (row < rows && w < M.D) M.w[row * M.D + w] = v[t];
     }
-    rsync<WG>();
+    rsync<false>();
 }
 
 template <int G, int RT>
@@ -451,7 +348,6 @@ __device__ void lds_to_regs(const Mat &M, uint32_t (&v)[RT], int rows) {
         v[t] = (row < rows && w < M.D) ? M.w[row * M.D + w] : 0u;
     }
 }
-
 
 // Forward operands of one piece for the current row count r: this lane's dword of the initial row
 // [coeffs | unit vector of slot pc] and its quotients M[r][i] = coefficient i (i = G·t + g < r); with few
@@ -525,13 +421,8 @@ __device__ __forceinline__ uint32_t dot_chunked(const uint32_t *tab, const uint3
 
 // Runs pieces pc, pc+1, ... on the registers while the matrix stays a clean RREF (the next piece's forward
 // operands are loaded while the current one finishes).  Returns the next piece index; on leaving the clean
-// state (a kept row with a zero diagonal) the whole matrix is written back to LDS and *clean = false.
-#ifndef RLNC_SMALL_PRIO
-#define RLNC_SMALL_PRIO 1
-#endif
-constexpr bool kSmallPrio = RLNC_SMALL_PRIO != 0;
-
-template <int G, int RT, bool WG = true>
+// state (a kept row with a zero diagonal) the whole matrix is written back to LDS and *clean = false.  One wave.
+template <int G, int RT>
 __device__ int reg_run(const Mat &M, const uint32_t *tab, uint32_t (&v)[RT], const uint8_t *H, int pc, int m, int k,
                        int &rows, bool &clean, int32_t *St) {
     constexpr int DP = 64 / G;
@@ -544,18 +435,16 @@ __device__ int reg_run(const Mat &M, const uint32_t *tab, uint32_t (&v)[RT], con
     pc = __builtin_amdgcn_readfirstlane(pc);  // uniform piece index: scalar loop control
     load_fwd<G, RT>(M, tab, H, pc, rows, k, f);
     for (; pc < m; ++pc) {
-        if constexpr (!WG) {
+        {
             // one wave per object, several objects per SIMD (the small-object kernel): a wave that has fallen behind
             // wins issue over one ahead of it -- priority 3 for the first quarter of the pieces down to 0 for the last
             // -- so the SIMD's objects finish together instead of one straggler setting the kernel's end
-            // (RLNC_SMALL_PRIO diagnostic knob: the A/B build compiles both)
-            if (kSmallPrio) {  // s_setprio takes an immediate: step down at the quarter marks
-                const int q4 = 4 * pc;
-                if (q4 < m) __builtin_amdgcn_s_setprio(3);
-                else if (q4 < 2 * m) __builtin_amdgcn_s_setprio(2);
-                else if (q4 < 3 * m) __builtin_amdgcn_s_setprio(1);
-                else __builtin_amdgcn_s_setprio(0);
-            }
+            // (s_setprio takes an immediate: step down at the quarter marks)
+            const int q4 = 4 * pc;
+            if (q4 < m) __builtin_amdgcn_s_setprio(3);
+            else if (q4 < 2 * m) __builtin_amdgcn_s_setprio(2);
+            else if (q4 < 3 * m) __builtin_amdgcn_s_setprio(1);
+            else __builtin_amdgcn_s_setprio(0);
         }
         const int r = __builtin_amdgcn_readfirstlane(rows);  // uniform: scalar branches and shift amounts below
         if (r == k) {  // decoder.rs:97-99
@@ -578,9 +467,9 @@ __device__ int reg_run(const Mat &M, const uint32_t *tab, uint32_t (&v)[RT], con
             const bool keep = ballot((nr & cm) != 0) != 0;  // remove_zero_rows (:222-244)
             if (lane == 0) St[pc] = keep ? RLNC_OK : RLNC_ERR_PIECE_NOT_USEFUL;
             if (keep) {  // the row survives with a zero diagonal: leave the clean state (generic path)
-                regs_to_lds<G, RT, WG>(M, v, r);
+                regs_to_lds<G, RT>(M, v, r);
                 if (g == 0 && wl) M.w[r * M.D + w] = nr;
-                rsync<WG>();
+                rsync<false>();
                 rows = r + 1;
                 clean = false;
                 return pc + 1;
@@ -619,131 +508,6 @@ __device__ int reg_run(const Mat &M, const uint32_t *tab, uint32_t (&v)[RT], con
     return pc;
 }
 
-// staged headers: m × k bytes after the matrix (hdr_lds = 1), else read from global memory per piece
-// ---------------------------------------------------------------------------------------------------
-// Multi-wave clean run (k <= 32, row <= 16 dwords): the same products as reg_run, with the matrix rows spread
-// over NW waves (wave s, lane (w, g), register t holds dword w of row 8s + 4t + g).  Per piece: each wave's
-// forward partial sum is reduced inside the wave, the NW partials meet in LDS (one barrier per piece, two
-// buffers), every wave finishes the new row redundantly, then updates its own rows (backward).  A wave's VALU
-// work per piece is 1/NW of the single-wave path's.  Returns the next piece index; on exit (all pieces done,
-// or a kept row with a zero diagonal ends the clean state) the whole matrix is in LDS.
-// ---------------------------------------------------------------------------------------------------
-template <int NW, int MG, int RTW>
-__device__ int reg_run_mw(const Mat &M, const uint32_t *tab, const uint8_t *H, uint32_t *P, int m, int k, int &rows,
-                          bool &clean, int32_t *St) {
-    constexpr int G = MG, DP = 64 / MG;
-    constexpr bool kPre = RTW <= 8;  // few rows per lane: the next piece's forward tables are prefetched
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const int w = lane % DP, g = lane / DP;
-    const bool wl = w < M.D;
-    uint32_t cm = 0;  // coefficient bytes (< k) of this lane's dword
-    if (wl && 4 * w < k) cm = 4 * w + 4 <= k ? 0xFFFFFFFFu : (0xFFFFFFFFu >> (8 * (4 * w + 4 - k)));
-    uint32_t v[RTW];
-#pragma unroll
-    for (int t = 0; t < RTW; ++t) v[t] = 0;
-    auto row_of = [&](int t) { return RTW * G * wave + G * t + g; };
-    // forward operands of piece pc for row count r: init dword w, quotients M[r][i] of own rows (and tables)
-    uint32_t init = 0, q[RTW], t2[kPre ? RTW : 1];
-    uint4 t4[kPre ? RTW : 1];
-    auto load_ops = [&](int pc, int r) {
-        const uint8_t *h = H + pc * k;
-#pragma unroll
-        for (int t = 0; t < RTW; ++t) q[t] = row_of(t) < r ? uint32_t(h[row_of(t)]) : 0u;
-        uint32_t x = 0;
-        if (wl) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-                const int c = 4 * w + b;
-                x |= (c < k ? uint32_t(h[c]) : uint32_t(c == k + pc)) << (8 * b);
-            }
-        }
-        init = x;
-        if constexpr (kPre) {
-#pragma unroll
-            for (int t = 0; t < RTW; ++t) {
-                t4[t] = *reinterpret_cast<const uint4 *>(tab + q[t] * kTabDw);
-                t2[t] = tab[q[t] * kTabDw + 4];
-            }
-        }
-    };
-    auto to_lds = [&](int nrows) {
-#pragma unroll
-        for (int t = 0; t < RTW; ++t)
-            if (row_of(t) < nrows && wl) M.w[row_of(t) * M.D + w] = v[t];
-    };
-    int buf = 0, pc = 0;
-    load_ops(0, 0);
-    for (; pc < m; ++pc) {
-        const int r = rows;
-        if (r == k) {  // decoder.rs:97-99
-            if (threadIdx.x == 0) St[pc] = RLNC_ERR_RECEIVED_ALL_PIECES;
-            continue;
-        }
-        uint32_t acc = 0;
-        if constexpr (kPre) {
-#pragma unroll
-            for (int t = 0; t < RTW; ++t) acc ^= mul4t(t4[t], t2[t], v[t]);
-        } else {
-            acc = dot_chunked<RTW>(tab, q, v);
-        }
-        acc = group_xor<DP>(acc);
-        uint32_t *Pb = P + buf * NW * DP;
-        if (lane < DP) Pb[wave * DP + lane] = acc;
-        __syncthreads();
-        uint32_t nr = init;
-#pragma unroll
-        for (int s = 0; s < NW; ++s) nr ^= Pb[s * DP + w];
-        buf ^= 1;
-        const int rw = r >> 2, rb = 8 * (r & 3);
-        const uint32_t piv = __builtin_amdgcn_readfirstlane((__builtin_amdgcn_readlane(nr, rw) >> rb) & 0xFFu);
-        if (piv == 0) {
-            const bool keep = ballot((nr & cm) != 0) != 0;  // remove_zero_rows (:222-244)
-            if (threadIdx.x == 0) St[pc] = keep ? RLNC_OK : RLNC_ERR_PIECE_NOT_USEFUL;
-            if (keep) {  // leave the clean state: the matrix goes to LDS for the single-wave generic path
-                to_lds(r);
-                if (wave == 0 && g == 0 && wl) M.w[r * M.D + w] = nr;
-                __syncthreads();
-                rows = r + 1;
-                clean = false;
-                return pc + 1;
-            }
-            if (pc + 1 < m) load_ops(pc + 1, r);
-            continue;
-        }
-        const uint4 ti4 = *reinterpret_cast<const uint4 *>(tab + (256 + piv) * kTabDw);
-        const uint32_t ti2 = tab[(256 + piv) * kTabDw + 4];
-        const uint32_t mask = from_mask(w, r + 1);
-        nr = (nr & ~mask) | (mul4t(ti4, ti2, nr) & mask);
-        if (w == rw) nr = (nr & ~(0xFFu << rb)) | (1u << rb);
-        rows = r + 1;
-#pragma unroll
-        for (int c0 = 0; c0 < RTW; c0 += 8) {  // backward in chunks of 8 rows (table reads issued together)
-            constexpr int U = RTW < 8 ? RTW : 8;
-            uint4 b4[U];
-            uint32_t b2[U];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                const uint32_t qb = (__shfl(v[c0 + u], rw + DP * g) >> rb) & 0xFFu;  // M[row][r], row in this wave
-                b4[u] = *reinterpret_cast<const uint4 *>(tab + qb * kTabDw);
-                b2[u] = tab[qb * kTabDw + 4];
-            }
-            if (c0 == 0 && pc + 1 < m) load_ops(pc + 1, r + 1);
-#pragma unroll
-            for (int u = 0; u < U; ++u) v[c0 + u] ^= mul4t(b4[u], b2[u], nr);
-        }
-#pragma unroll
-        for (int t = 0; t < RTW; ++t)
-            if (row_of(t) == r) v[t] = nr;
-        if (threadIdx.x == 0) St[pc] = RLNC_OK;
-    }
-    to_lds(rows);
-    __syncthreads();
-    return pc;
-}
-
-// G > 0: the clean state runs on registers (reg_run<G, RT>); G = 0: on LDS (clean_append).  NW > 1: the
-// initial clean run is spread over NW waves (reg_run_mw); then waves 1..NW-1 end and wave 0 continues alone
-// (S_BARRIER waits only for the waves that have not terminated).
 // ragged batch (p.objs): this workgroup's object replaces the uniform fields, as object 0 of a one-object batch
 __device__ __forceinline__ void rref_ragged_object(RrefParams &p, int &o) {
     if (p.objs == nullptr) return;
@@ -766,12 +530,13 @@ __device__ __forceinline__ void rref_ragged_object(RrefParams &p, int &o) {
     o = 0;
 }
 
-template <int G, int RT, int NW, int MG = 4, int MRTW = 2>
-__global__ __launch_bounds__(64 * NW) void gf_rref_batch_kernel(RrefParams p, int hdr_lds) {
+// The one-wave LDS kernel: one object per workgroup of one wave, the matrix in LDS -- clean_append while the clean
+// state holds, the reference's rref verbatim (generic_rref) outside it.  hdr_lds = 1: all m headers staged in LDS
+// after the statuses (m × k bytes), else each is read from global memory when its piece comes up.
+__global__ __launch_bounds__(64) void gf_rref_batch_kernel(RrefParams p, int hdr_lds) {
     extern __shared__ uint32_t lds[];
     uint32_t *tab = lds;  // kTabEntries × kTabDw dwords
-    const int lane = threadIdx.x;  // the single-wave code below runs in wave 0 only (lane < 64)
-    const int tid = threadIdx.x;
+    const int lane = threadIdx.x;
     int o = blockIdx.x;
     rref_ragged_object(p, o);
     if (p.skip_full && p.rank[o] >= p.k) return;  // two-pass: the blocked pass already full-ranked this object
@@ -785,56 +550,37 @@ __global__ __launch_bounds__(64 * NW) void gf_rref_batch_kernel(RrefParams p, in
     // its release fence wait for the store to reach memory, once per piece
     int32_t *St = reinterpret_cast<int32_t *>(M.b + size_t(k + 1) * M.S);
     uint8_t *H = reinterpret_cast<uint8_t *>(St + ((m + 3) & ~3));
-    // NW > 1: two buffers of NW × 16 forward partial sums after the staged headers
-    uint32_t *P = reinterpret_cast<uint32_t *>(H + ((size_t(m) * k + 15) & ~size_t(15)));
 
     {  // all loads of the table copy in flight at once (one memory latency, not one per iteration)
-        constexpr int kPer = kTabEntries * kTabDw / 4 / (64 * NW);
+        constexpr int kPer = kTabEntries * kTabDw / 4 / 64;
         const uint4 *src = reinterpret_cast<const uint4 *>(kRrefTable.v);
         uint4 *dst = reinterpret_cast<uint4 *>(tab);
         uint4 t4[kPer];
 #pragma unroll
-        for (int u = 0; u < kPer; ++u) t4[u] = src[tid + 64 * NW * u];
+        for (int u = 0; u < kPer; ++u) t4[u] = src[lane + 64 * u];
 #pragma unroll
-        for (int u = 0; u < kPer; ++u) dst[tid + 64 * NW * u] = t4[u];
+        for (int u = 0; u < kPer; ++u) dst[lane + 64 * u] = t4[u];
     }
     const uint8_t *base = p.pieces + int64_t(o) * p.obj_stride;
     if (hdr_lds) {  // 16 independent byte loads in flight per batch
-        for (int e0 = 0; e0 < m * k; e0 += 64 * NW * 16) {
+        for (int e0 = 0; e0 < m * k; e0 += 64 * 16) {
             uint8_t hb[16];
 #pragma unroll
             for (int u = 0; u < 16; ++u) {
-                const int e = e0 + tid + 64 * NW * u;
+                const int e = e0 + lane + 64 * u;
                 hb[u] = e < m * k ? base[int64_t(e / k) * p.piece_stride + e % k] : uint8_t(0);
             }
 #pragma unroll
             for (int u = 0; u < 16; ++u)
-                if (e0 + tid + 64 * NW * u < m * k) H[e0 + tid + 64 * NW * u] = hb[u];
+                if (e0 + lane + 64 * u < m * k) H[e0 + lane + 64 * u] = hb[u];
         }
     }
-    for (int w = tid; w < (k + 1) * M.D; w += 64 * NW) M.w[w] = 0;
+    for (int w = lane; w < (k + 1) * M.D; w += 64) M.w[w] = 0;
     __syncthreads();
 
     int rows = 0;
     bool clean = true;
-    int pc0 = 0;
-    if constexpr (NW > 1) {
-        pc0 = reg_run_mw<NW, MG, MRTW>(M, tab, H, P, m, k, rows, clean, St);
-        if (threadIdx.x >= 64) return;  // wave 0 finishes alone (generic path / output)
-    }
-    uint32_t v[G > 0 ? RT : 1];
-#pragma unroll
-    for (int t = 0; t < (G > 0 ? RT : 1); ++t) v[t] = 0;
-    if constexpr (NW > 1 && G > 0)
-        if (clean && rows > 0 && pc0 < m) lds_to_regs<G, RT>(M, v, rows);
-    for (int pc = pc0; pc < m; ++pc) {
-        if constexpr (G > 0) {
-            if (clean) {
-                pc = reg_run<G, RT>(M, tab, v, H, pc, m, k, rows, clean, St);
-                __syncthreads();
-                if (pc >= m) break;
-            }
-        }
+    for (int pc = 0; pc < m; ++pc) {
         if (rows == k) {  // decoder.rs:97-99
             if (lane == 0) St[pc] = RLNC_ERR_RECEIVED_ALL_PIECES;  // ReceivedAllPieces
             continue;
@@ -849,21 +595,17 @@ __global__ __launch_bounds__(64 * NW) void gf_rref_batch_kernel(RrefParams p, in
         }
         __syncthreads();
         const int before = rows;
-        if (G == 0 && clean) {
+        if (clean) {
             bool sc;
             rows = clean_append(M, tab, rows, k, &sc);
             clean = sc;
         } else {
             rows = generic_rref(M, tab, rows + 1, k);
             clean = is_clean(M, rows);
-            if constexpr (G > 0)
-                if (clean) lds_to_regs<G, RT>(M, v, rows);
         }
         if (lane == 0) St[pc] = rows == before ? RLNC_ERR_PIECE_NOT_USEFUL : RLNC_OK;  // decoder.rs:112-117
         __syncthreads();
     }
-    if constexpr (G > 0)
-        if (clean && pc0 < m) regs_to_lds<G, RT>(M, v, rows);
     __syncthreads();
     for (int pc = lane; pc < m; pc += 64) p.status[int64_t(o) * m + pc] = St[pc];
     if (lane == 0) p.rank[o] = rows;
@@ -874,12 +616,11 @@ __global__ __launch_bounds__(64 * NW) void gf_rref_batch_kernel(RrefParams p, in
     }
 }
 
-
 // Many small objects (row <= 16 dwords, k <= 16): NW objects per workgroup, one per wave, over ONE LDS copy of the
 // multiplier table.  The one-wave kernel above copies the 16 KiB table per object, which caps a CU at 8 resident
 // objects; here a workgroup of 4 holds 4 objects in ~20 KiB, so all 16 objects per CU of a 4,096-object batch are
-// resident at once.  Per wave the same steps as gf_rref_batch_kernel<4, 8, 1> (register clean run, the reference's
-// rref verbatim when the clean state ends), with wave-local synchronisation only: after the table copy no wave
+// resident at once.  Per wave: the register clean run (reg_run), and the reference's rref decomposed around the
+// clean prefix when the clean state ends (small_dirty_step), with wave-local synchronisation only: after the table copy no wave
 // waits for another.
 // the payload-tail staging of one object (RrefParams::tail_status): the last 64 data bytes of each of its m pieces,
 // moved into LDS by DMA at the kernel's start (a valid payload's marker lies in its last k <= 16 bytes)
@@ -1065,15 +806,13 @@ __device__ void small_dirty_step(const Mat &M, const uint32_t *tab, const uint8_
     cp = extend_prefix(M, r0, rows);
 }
 
-template <int NW, int G, int RT, bool PROF = false>
+template <int NW, int G, int RT>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(G == 8 ? 4 : 1))) void gf_rref_small_kernel(RrefParams p) {
     extern __shared__ uint32_t lds[];
     uint32_t *tab = lds;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    uint64_t ts[6] = {};  // PROF (diagnostic build): wave start, table copied, headers staged, pieces done, end
-    if constexpr (PROF) ts[0] = wall_clock64();
     const int o = blockIdx.x * NW + wave;
-    const int k = p.k, m = p.m;  // k <= 16 and k + m <= 64 on this path (rref.hip small_many)
+    const int k = p.k, m = p.m;  // k <= 16 and k + m <= 64 on this path (launch_rref_one)
     // this object's headers first (lane = piece, its k <= 16 coefficient bytes in flight at once, no index
     // division), then the shared table copy: both global-load latencies overlap
     uint8_t hb[16];
@@ -1117,7 +856,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(G == 8 
                                              0);
     }
     __syncthreads();  // the only workgroup barrier: the table, and this wave's headers and zeroed matrix
-    if constexpr (PROF) ts[1] = ts[2] = wall_clock64();
     if (o >= p.n_obj) return;
 
     int rows = 0, cp = -1;  // cp: the clean prefix while outside the clean state (-1 inside it)
@@ -1127,7 +865,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(G == 8 
     for (int t = 0; t < RT; ++t) v[t] = 0;
     for (int pc = 0; pc < m; ++pc) {
         if (clean) {
-            pc = reg_run<G, RT, false>(M, tab, v, H, pc, m, k, rows, clean, St);
+            pc = reg_run<G, RT>(M, tab, v, H, pc, m, k, rows, clean, St);
             rsync<false>();
             if (pc >= m) break;
         }
@@ -1139,7 +877,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(G == 8 
         // (rows < cp) + dirty rows, decomposed around the prefix (small_dirty_step)
         if (cp < 0) cp = rows - 1;  // reg_run left the clean state: its last kept row is the first dirty one
         const int before = rows;
-        if constexpr (PROF) ++ts[5];  // pieces outside the clean state
         small_dirty_step(M, tab, H + pc * k, pc, k, rows, cp);
         clean = cp == rows;
         if (clean) {
@@ -1149,7 +886,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(G == 8 
         if (lane == 0) St[pc] = rows == before ? RLNC_ERR_PIECE_NOT_USEFUL : RLNC_OK;  // decoder.rs:112-117
         rsync<false>();
     }
-    if (clean) regs_to_lds<G, RT, false>(M, v, rows);
+    if (clean) regs_to_lds<G, RT>(M, v, rows);
     rsync<false>();
     // RrefParams::tail_status: the marker scan's answer from the payload tail -- before this wave's stores below, so
     // that the wait for the staging DMAs does not wait for them too
@@ -1189,7 +926,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(G == 8 
             }
         }
     }
-    if constexpr (PROF) ts[3] = wall_clock64();
     for (int pc = lane; pc < m; pc += 64) p.status[int64_t(o) * m + pc] = St[pc];
     if (lane == 0) p.rank[o] = rows;
     if (p.tail_status != nullptr && lane == 0) {
@@ -1207,12 +943,6 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(G == 8 
         const int r = lane & (tr - 1), step = 64 / tr;
         for (int s = lane / tr; s < m; s += step)
             st[s * tr + r] = (r < rows ? uint32_t(M.b[r * M.S + k + s]) : 0u) * p.bsj_block_bytes;
-    }
-    if constexpr (PROF) {
-        ts[4] = wall_clock64();
-        ts[5] |= uint64_t(__smid()) << 32;
-        if (lane < 6) p.prof[int64_t(o) * 8 + lane] = ts[lane];
-        if (lane == 6) p.prof[int64_t(o) * 8 + 6] = uint64_t(rows);
     }
 }
 
@@ -1593,15 +1323,19 @@ __global__ __launch_bounds__(64 * NW) void gf_rref_block_kernel(RrefParams p) {
     }
 }
 
-constexpr int kBlkNW = 4, kBlkB = 16, kBlkDefault = 8;
+constexpr int kBlkNW = 4, kBlkB = 8;  // waves per object and pieces per block of the blocked run
+// The two LDS budgets below are also the paths' eligibility limits (rref_block_eligible, the staged-header test), which
+// callers and tests mirror, so they keep counting what the retired forms needed: X rows for 16-piece blocks (the kernel
+// uses the first kBlkB), and 2 KiB of partial sums behind the staged headers (unused).
+constexpr int kBlkXRows = 16;
 
 size_t rref_block_lds_bytes(int k, int m) {
     const int D = rref_row_dwords(k, m);
     return size_t(kTabEntries) * kTabDw * 4 + size_t(k + 1) * 4 * D + 4 * ((size_t(m) + 3) & ~size_t(3)) +
-           ((size_t(m) * ((k + 3) & ~3) + 15) & ~size_t(15)) + size_t(kBlkB) * D * 4 + 16;
+           ((size_t(m) * ((k + 3) & ~3) + 15) & ~size_t(15)) + size_t(kBlkXRows) * D * 4 + 16;
 }
 
-inline size_t rref_lds_bytes_staged(int k, int m) {  // + the staged headers, + 2 × 4 × 64 dwords of partial sums
+inline size_t rref_lds_bytes_staged(int k, int m) {  // + the staged headers
     return rref_lds_bytes(k, m) + ((size_t(k) * m + 15) & ~size_t(15)) + 2 * 4 * 64 * 4;
 }
 

@@ -1,11 +1,11 @@
 #!/usr/bin/env python3
 """Device elimination (rlnc_decode_batch_eliminate) time per decode path and shape, HIP events on the launch stream,
-median of 7 launches after 2 warm-ups; every path's statuses, ranks and T checked equal to path 2's (the round-1
-default) on the same pieces.  Shapes: the bench's (32 objects, k = m = 32), configs[4]'s per-GPU share
+median of 7 launches after 2 warm-ups; every path's statuses, ranks and T checked equal to the first path's on the
+same pieces.  Paths: 0 (the default: chosen by shape), 2 (the device), 5 (the blocked run, k + m <= 256 only).  Shapes: the bench's (32 objects, k = m = 32), configs[4]'s per-GPU share
 (512 objects, k = m = 128), configs[0]'s shape batched (4,096 objects, k = m = 16), plus random sparse and
 dependent pieces that leave the clean state.  One JSON line per (shape, path).
 
-    ELIM_PATHS=2,5 python scripts/elim_timing.py
+    ELIM_PATHS=0,5 python scripts/elim_timing.py
 """
 import json
 import os
@@ -25,7 +25,7 @@ SHAPES = [  # name, objects, k, m, sparsity, dependent fraction
     ("k128 sparse 0.9", 64, 128, 128, 0.9, 0.02),
     ("configs[4] share k128, LU (never leaves the clean state)", 512, 128, 128, -1.0, 0.0),
 ]
-if os.environ.get("ELIM_SHAPES") == "small":  # small-k crossover of the one-wave register kernel (path 4)
+if os.environ.get("ELIM_SHAPES") == "small":  # small-k crossover of the small-object kernel
     SHAPES = [("k8 x4096", 4096, 8, 8, 0.0, 0.0), ("k16 x4096", 4096, 16, 16, 0.0, 0.0),
               ("k16 x512", 512, 16, 16, 0.0, 0.0), ("k16 m24 sparse 0.5 dep", 4096, 16, 24, 0.5, 0.1),
               ("k24 x2048", 2048, 24, 24, 0.0, 0.0), ("k32 x1024", 1024, 32, 32, 0.0, 0.0),
@@ -62,7 +62,7 @@ def main():
     from rlnc_amd import batch
 
     ctx = rlnc_amd.Context(0)
-    paths = [int(x) for x in os.environ.get("ELIM_PATHS", "6,5").split(",")]
+    paths = [int(x) for x in os.environ.get("ELIM_PATHS", "2,5").split(",")]
     L = 16  # the elimination reads only the coefficient bytes
     for name, B, k, m, sp, dep in SHAPES:
         rng = np.random.default_rng(k * 7 + m)

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Elimination-kernel cost vs pieces per object (m = 1, 4, 16, 32; k = 32, 16 objects, uniform coefficients):
-run under `rocprofv3 --kernel-trace` and read gf_rref_batch_kernel's duration per m (intercept = setup, slope =
-per piece).  Decode path via RREF_PATH (2 multi-wave registers, 4 one-wave registers, 3 LDS)."""
+run under `rocprofv3 --kernel-trace` and read the elimination kernel's duration per m (intercept = setup, slope =
+per piece).  Decode path via RREF_PATH (2 the device elimination as chosen by shape, 5 the blocked run)."""
 import os
 import sys
 

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Cost of the device elimination (gf_rref_batch_kernel) by coefficient structure.
+"""Cost of the device elimination (rref.hip) by coefficient structure.
 
 Decodes 16 objects (k = 32, first 32 coded pieces, L = 64 KiB so the T × D product is small) whose coding
 vectors are (a) unit upper triangular — every piece keeps the matrix a clean RREF, (b) uniform random (the
@@ -42,8 +42,8 @@ def main():
     dirty[:, 1, :] = 0
     dirty[:, 1, 2] = 5  # reduced by row 0 (column 0 is zero) -> diagonal M[1][1] = 0, column 2 nonzero: kept
     cases["dirty_from_piece_1"] = dirty
-    # 2 registers (multi-wave initial clean run), 3 LDS clean state, 4 registers on one wave
-    paths = [int(x) for x in os.environ.get("RREF_PATHS", "2,4,3").split(",")]
+    # 2 the device elimination as chosen by shape, 5 the blocked run
+    paths = [int(x) for x in os.environ.get("RREF_PATHS", "2,5").split(",")]
     for (name, co), path in [(c, p) for c in cases.items() for p in paths]:
         ctx.set_decode_path(path)
         pieces = torch.empty((B, m, k + L), dtype=torch.uint8, device="cuda")

@@ -299,6 +299,80 @@ def test_rref_lds_borders(ctx0, k, m):
             eliminate(ctx0, pieces_t, k)
 
 
+# ---- rref.hip: one case per outcome of its dispatch (launch_rref_one and the two-pass wrapper; rank mode 0) -----------
+
+SMALL_MIN_OBJECTS = 2048  # kSmallMinObjects (rref_kernels.hpp)
+# name -> (k, m, objects)
+RREF_OUTCOMES = {
+    "blocked": (16, 18, 3),
+    "small-8-dwords": (8, 10, SMALL_MIN_OBJECTS),
+    "small-16-dwords": (16, 40, SMALL_MIN_OBJECTS),
+    "two-pass": (128, 130, 2),
+    "lds-staged": (130, 132, 2),
+    "lds-unstaged": (224, 228, 2),
+}
+
+
+@functools.lru_cache(maxsize=None)
+def outcome_case(name):
+    """(pieces [nobj][m][k + m], per object (statuses, rank, T)) of one shape of RREF_OUTCOMES, computed once and left
+    unchanged.  Piece j carries the unit vector e_j as its data, so the oracle's payload rows are T's rows.  Every
+    object has a piece that is a combination of two earlier ones: piece 5 in odd objects, piece k / 2 in even ones (in
+    the two-pass shape the last piece, so that the first 128 pieces alone reach rank k); every fourth object (the
+    second, where there are two) has half of its coefficients zero, which takes the matrix out of the clean state."""
+    k, m, nobj = RREF_OUTCOMES[name]
+    rng = np.random.default_rng(k * 1000 + m)
+    co = rng.integers(0, 256, (nobj, m, k), dtype=np.uint8)
+    for o in range(nobj):
+        if o % 4 == 1:
+            co[o][rng.random((m, k)) < 0.5] = 0
+        d = 5 if o % 2 else m - 1 if name == "two-pass" else k // 2
+        co[o, d] = co[o, 1] ^ ls.MUL[int(rng.integers(2, 256))][co[o, 3]]
+    pieces = np.concatenate([co, np.broadcast_to(np.eye(m, dtype=np.uint8), (nobj, m, m))], axis=2)
+    want = []
+    for o in range(nobj):
+        od = OracleDecoder(m, k)
+        st = [od.decode(p) for p in pieces[o]]
+        rows = od.padded_payload()
+        T = np.zeros((k, m), np.uint8)
+        T[:rows.shape[0]] = rows
+        want.append((st, rows.shape[0], T))
+    pieces.setflags(write=False)
+    return pieces, want
+
+
+@pytest.mark.parametrize("name", list(RREF_OUTCOMES))
+def test_rref_dispatch_outcomes(ctx0, name):
+    """decode_batch_eliminate on decode path 0, one shape per kernel choice of rref.hip, exact against the oracle on
+    statuses, rank and T.  Which choice a shape reaches is asserted on the mirrors of tests/limit_shapes.py: the
+    small-object kernel from 2,048 objects of k <= 16 on, in its 8-dword and 16-dword row shapes; the blocked run while
+    a row fits one wave (k + m <= 256); beyond that the two-pass split up to k = 128 (the first object reaches rank k
+    within the blocked pass, the second does not and is redone by the general pass); else the one-wave LDS kernel, with
+    the headers staged in LDS where they fit beside the matrix and without where only the matrix fits.  The borders of
+    the two LDS forms themselves are test_rref_lds_borders' (other shapes); none of these six runs elsewhere in this
+    module."""
+    k, m, nobj = RREF_OUTCOMES[name]
+    D = ls.rref_row_dwords(k, m)
+    small = k <= 16 and nobj >= SMALL_MIN_OBJECTS and D <= 16
+    reached = ("small-8-dwords" if small and D <= 8 else "small-16-dwords" if small else "blocked" if D <= 64 else
+               "two-pass" if k <= 128 else
+               "lds-staged" if ls.rref_lds_bytes_staged(k, m) <= ls.MAX_LDS else "lds-unstaged")
+    assert reached == name
+    assert ls.rref_lds_bytes(k, m) <= ls.MAX_LDS
+    pieces, want = outcome_case(name)
+    if name == "two-pass":  # pass 1 replays the first 256 - k = 128 pieces
+        assert want[0][0] == [OK] * 128 + [RECEIVED_ALL] * 2 and NOT_USEFUL in want[1][0][:128]
+    else:
+        # the dependent piece of every dense object (the diagonal-pivot elimination may keep a sparse one's)
+        assert all(NOT_USEFUL in st for o, (st, _, _) in enumerate(want) if o % 4 != 1)
+    assert any(rank == k for _, rank, _ in want)
+    T, ps, rk = eliminate(ctx0, dev(pieces.copy()), k)
+    for o, (st, rank, Tw) in enumerate(want):
+        assert list(ps[o]) == st, o
+        assert rk[o] == rank, o
+        assert np.array_equal(T[o], Tw), o
+
+
 # ---- several beyond-LDS objects in the one workspace of a ragged decode ----------------------------------------------
 
 @functools.lru_cache(maxsize=None)

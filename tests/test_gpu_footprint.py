@@ -49,7 +49,7 @@ import pytest
 from oracle import np_oracle as npo
 from oracle.oracle import OracleDecoder
 from tests.footprint import Arena, assert_inputs_unchanged
-from tests.gpu_util import MUL, decode_paths, np_matmul, variants
+from tests.gpu_util import MUL, np_matmul, variants
 
 pytestmark = pytest.mark.gpu
 
@@ -434,7 +434,7 @@ def upload_pieces(objs):
     return allp, t, t[:, :m]
 
 
-@pytest.mark.parametrize("path", decode_paths(0, 1, 2, 5, 3, 4, 6))
+@pytest.mark.parametrize("path", [0, 1, 2, 5])
 @pytest.mark.parametrize("L", DECODE_LENGTHS)
 @pytest.mark.parametrize("k,m", DECODE_SHAPES)
 def test_decode_footprints(ctx, k, m, L, path):
@@ -953,10 +953,9 @@ def test_marker_scan_in_tile(ctx, nobj):
     """decode_batch_device at k = 4, L = 4096.  With 33 objects the blocked elimination runs and final_len_scan_kernel
     answers every object (four 1 KiB chunks a row).  From 2,048 objects on (here 2,049) the small-object elimination
     kernel answers the objects of rank < k and those with a nonzero byte in the last 64 payload bytes itself, and flags
-    the rest for bsj_tile_scan in the product's 1-wave tile (launch_rref_one's small_many; batch.cpp, written &&
+    the rest for bsj_tile_scan in the product's 1-wave tile (launch_rref_one's small-object branch; batch.cpp, written &&
     want_tail).  That case moves 2 x 33 MiB, beyond the 2 MiB the other cases keep to: the kernel is not reached with
-    fewer objects.  (In the diagnostic A/B build the elimination goes through launch_rref_ab, which never answers from
-    the tail: there both sizes end in final_len_scan_kernel.)"""
+    fewer objects."""
     import torch
 
     from rlnc_amd import batch

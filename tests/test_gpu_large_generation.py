@@ -311,10 +311,38 @@ def test_path_rules():
     from rlnc_amd import batch
     from rlnc_amd.errors import RLNCError
 
+    from oracle.oracle import OracleDecoder
+
     ctx = rlnc_amd.Context(0)  # rank mode 0
     with pytest.raises(RLNCError) as ei:
         ctx.set_decode_path(9)
     assert ei.value == RLNCError.InvalidArgument
+    # no such paths (3, 4 and 6 were the retired forms of the device elimination): refused, and the path set before
+    # stays in force -- path 5 still refuses a shape the blocked run does not take (path 0 would decode it), and still
+    # decodes k = 8, m = 9 as the oracle does
+    ctx.set_decode_path(5)
+    for p in (3, 4, 6, -1, 9):
+        with pytest.raises(RLNCError) as ei:
+            ctx.set_decode_path(p)
+        assert ei.value == RLNCError.InvalidArgument
+    with pytest.raises(RLNCError) as ei:
+        batch.decode_batch(dev(np.zeros((1, 130, 128 + 4), np.uint8)), 128,
+                           torch.zeros((1, 128, 4), dtype=torch.uint8, device="cuda:0"), ctx)
+    assert ei.value == RLNCError.InvalidArgument
+    rng = np.random.default_rng(89)
+    k, m, L = 8, 9, 16
+    data = rng.integers(0, 256, k * L - 3, dtype=np.uint8)
+    co = rng.integers(0, 256, (m, k), dtype=np.uint8)
+    co[4] = co[1] ^ MUL[7][co[2]]  # a dependent piece
+    seq = npo.encode(npo.pad(data, k), co)
+    dec = torch.zeros((1, k, L), dtype=torch.uint8, device="cuda:0")
+    pst, ost, dl = batch.decode_batch(dev(seq[None]), k, dec, ctx)
+    od = OracleDecoder(L, k)
+    assert list(pst[0]) == [od.decode(p) for p in seq]
+    assert np.array_equal(host(dec)[0], od.padded_payload())
+    st, got = od.get_decoded_data()
+    assert st == 0 and ost[0] == 0 and int(dl[0]) == data.size and np.array_equal(got, data)
+    ctx.set_decode_path(0)
     rng = np.random.default_rng(21)
     k, L = 6, 32
     src = npo.pad(rng.integers(0, 256, k * L - 3, dtype=np.uint8), k)

@@ -8,7 +8,7 @@ import pytest
 from oracle import np_oracle as npo
 from oracle.oracle import OracleDecoder
 from tests.conftest import hexarr
-from tests.gpu_util import AB_BUILD, MUL, decode_paths, dev, host, np_matmul, variants
+from tests.gpu_util import AB_BUILD, MUL, dev, host, np_matmul, variants
 
 pytestmark = pytest.mark.gpu
 
@@ -353,7 +353,7 @@ def test_golden_decode_object_api(ctx, golden):
             assert e.name == v["final_status"], v["name"]
 
 
-@pytest.mark.parametrize("path", decode_paths(1, 2, 3, 4, 5, 6))
+@pytest.mark.parametrize("path", [1, 2, 5])
 def test_golden_decode_batch(ctx, golden, path):
     from rlnc_amd import batch
 
@@ -393,7 +393,7 @@ def _sequences(rng, nobj, k, m, L, sparsity, dep_frac):
     return seqs
 
 
-@pytest.mark.parametrize("path", decode_paths(1, 2, 3, 4, 5, 6))
+@pytest.mark.parametrize("path", [1, 2, 5])
 @pytest.mark.parametrize("k,m,L,sparsity,dep", [(32, 32, 40, 0.0, 0.0), (64, 64, 24, 0.0, 0.1), (128, 128, 20, 0.0, 0.0),
                                                 (100, 120, 9, 0.0, 0.1), (120, 128, 16, 0.9, 0.02),
                                                 (48, 56, 10, 0.4, 0.1), (64, 70, 9, 0.85, 0.05), (8, 14, 5, 0.7, 0.1), (8, 12, 33, 0.9, 0.0), (32, 40, 64, 0.0, 0.2),
