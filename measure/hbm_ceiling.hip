@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void read_kernel(const u32x4_t *src, u32x4_t *
     out[size_t(blockIdx.x) * 256 + threadIdx.x] = acc;
 }
 
-// grid = objects × column blocks (XCD-aware as decode_block in kernels.hip), k rows of stride L per block
+// grid = objects × column blocks (XCD-aware as decode_block in kernels_common.hpp), k rows of stride L per block
 __global__ __launch_bounds__(256) void pattern_kernel(const uint8_t *src, uint8_t *out, int k, int64_t L, int col_blocks,
                                                       int total) {
     int b = blockIdx.x, w = b;

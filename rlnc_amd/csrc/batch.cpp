@@ -170,7 +170,7 @@ int decode_eliminate_impl(rlnc_context *ctx, const uint8_t *pieces, size_t obj_s
     if (ctx->decode_path == 5 && !rlnc::rref_block_eligible(int(k), int(m)))  // no silent fallback to another kernel
         return set_error(RLNC_ERR_INVALID_ARGUMENT, "decode path 5 (blocked run) needs k + m <= 256 (k=%zu, m=%zu)", k, m);
     rp.bsj_stream = bsj;
-    rp.bsj_block_bytes = rlnc::bsj_block_bytes_public();
+    rp.bsj_block_bytes = rlnc::bsj_block_bytes();
     rp.bsj_tile_rows = bsj_rows;
     if (tail != nullptr) {
         rp.tail_status = tail->status;

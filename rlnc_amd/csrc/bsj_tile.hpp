@@ -1,6 +1,7 @@
 // bsj_tile.hpp — the tile body of the bit-sliced jump programs (the generated inline-asm programs of
-// bitslice_jump.inc, gen_bsjump.py): one workgroup's output rows x one 4 KiB column block.  Shared by the uniform and
-// ragged kernels of kernels.hip and the column-run A/B variant of kernels_ab.hip (internal to librlnc_hip).
+// bitslice_jump.inc, gen_bsjump.py): one workgroup's output rows x one 4 KiB column block.  Shared by the uniform
+// kernels of kernels.hip, the ragged ones of ragged.hip and the column-run A/B variant of kernels_ab.hip (internal to
+// librlnc_hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -10,6 +11,7 @@
 #include "bitslice_jump.inc"
 #include "gf256.hpp"
 #include "kernels.hpp"
+#include "kernels_common.hpp"
 
 #ifndef RLNC_BSJ_SOFFSETS
 #error "bitslice_jump.inc must be generated with packed blocks (gen_bsjump.py default)"
@@ -20,6 +22,9 @@ namespace {
 
 constexpr int kBsjWaveRows = RLNC_BSJ_NT;  // output rows per wave; a workgroup of W waves = 8 W rows
 constexpr int kBsjColBlock = 4096;          // 64 lanes × 64 B, shared by the W waves
+// The shared programs' blocks are packed at their own sizes (gen_bsjump.py), at these offsets from the table base (a
+// copy per translation unit: the offset kernels of kernels.hip and ragged.hip read it)
+__constant__ uint32_t kBsjSharedOff[256] = RLNC_BSJ_SOFFSETS;
 
 // SHARE (W = 4 only): wave w builds one of the four combination sets of each source row and the sets are
 // exchanged through LDS (RLNC_BSJ_ASM_W4S) instead of every wave building all four
@@ -95,14 +100,7 @@ __device__ __forceinline__ void bsj_tile(const MatmulParams &p, const void *stre
     __shared__ __attribute__((aligned(16))) uint8_t cset[SHARE ? (W == 8 ? RLNC_BSJ_CSET_BYTES8 : RLNC_BSJ_CSET_BYTES) : 16];
     const int row0 = rt * kTileRows;
     const int rows = min(kTileRows, p.n_out - row0);
-    if (p.hdr != nullptr && cb == 0) {  // coded-piece header (encoder.rs:246-248), 64·W threads
-        const uint8_t *coef_base = p.coef + int64_t(obj) * p.coef_obj + int64_t(row0) * p.coef_row;
-        uint8_t *h = p.hdr + int64_t(obj) * p.hdr_obj + int64_t(row0) * p.hdr_row;
-        for (int e = threadIdx.x; e < rows * p.n_in; e += 64 * W) {
-            const int i = e / p.n_in, j = e % p.n_in;
-            h[int64_t(i) * p.hdr_row + j] = coef_base[int64_t(i) * p.coef_row + j];
-        }
-    }
+    if (p.hdr != nullptr && cb == 0) copy_header_rows(p, obj, row0, rows, 64 * W);
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
     // the split 2-wave program (gen_bsjump.py --w2split): wave w owns the 2 KiB half w of the column block in all

@@ -21,6 +21,7 @@
 #include "../../include/rlnc_hip.h"
 #include "kernels.hpp"
 #include "rank_kernels.hpp"
+#include "rref.hpp"
 #include "rank_large_kernels.hpp"
 #include "sparse_kernels.hpp"
 

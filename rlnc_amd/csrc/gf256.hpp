@@ -46,7 +46,7 @@ struct HostField {
 
 const HostField &host_field();
 
-// The 3-bit-split product tables consumed by v_perm_b32 on device (see kernels.hip):
+// The 3-bit-split product tables consumed by v_perm_b32 on device (see perm_kernels.hpp):
 //   T0[v] = c·v        (v = 0..7)   -> bytes of {t0lo, t0hi}
 //   T1[v] = c·(v<<3)   (v = 0..7)   -> bytes of {t1lo, t1hi}
 //   T2[v] = c·(v<<6)   (v = 0..3)   -> bytes of t2

@@ -1,9 +1,9 @@
-// kernels.hpp — launch interface of the gfx950 kernels in kernels.hip (internal to librlnc_hip).
+// kernels.hpp — launch interface of the product (kernels.hip), the ragged batches (ragged.hip) and the element-wise
+// primitives and marker scan (elementwise.hip); internal to librlnc_hip.  The elimination's interface: rref.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
-#include <mutex>
 
 namespace rlnc {
 
@@ -76,16 +76,25 @@ bool unaligned_vector_ok();
 hipError_t launch_matmul(const MatmulParams &p, hipStream_t stream, MatmulVariant v = MatmulVariant::Perm,
                          void *scratch = nullptr, size_t scratch_bytes = 0);
 
-struct RrefParams;
-
 // ---- the A/B build (make ab: kernels_ab.hip adds matmul variants 2-5 and 9) ----
 // The shipped library defines these weakly (ab_build() false, the launches hipErrorInvalidValue); the A/B build's
 // definitions replace them.
 bool ab_build();
 hipError_t launch_matmul_ab(const MatmulParams &p, hipStream_t s, MatmulVariant v, void *scratch, size_t scratch_bytes);
 size_t matmul_scratch_bytes_ab(const MatmulParams &p, MatmulVariant v);
-// what the A/B variants reuse of the shipped bit-sliced jump path (kernels.hip): eligibility (whole 4 KiB column blocks
-// of aligned operands, >= 4 output rows), scratch size, and the block-address stream + launch geometry of a product
+// ---- the bit-sliced jump path (kernels.hip), as the A/B variants, the ragged batches and the decode reuse it ----
+// waves per workgroup (8 output rows each): 1, 2, 4 up to 32 output rows; wide (variant 8, the ragged batches): 8 above
+int bsj_waves(int n_out, bool wide);
+// eligibility (whole 4 KiB column blocks of aligned operands, >= 4 output rows) and scratch size of a product
+bool bsj_eligible(const MatmulParams &p, bool aligned);
+size_t bsj_scratch_bytes(const MatmulParams &p, bool wide);
+// block bytes and tile rows of the unshared programs (for RrefParams::bsj_*): tile rows 0 = not one of them
+uint32_t bsj_block_bytes();
+int bsj_unshared_tile_rows(int n_out);
+// Address of the shared-set programs' block table on the current device (scratch: >= 8 device bytes): one probe launch
+// per device, synchronous on s the first time only; base = 0 when that first time is inside a stream capture
+hipError_t bsj_shared_base(hipStream_t s, void *scratch, uint64_t &base);
+// the block-address stream + launch geometry of a product
 struct BsjPlan {
     int64_t full = 0;   // columns the bit-sliced program takes (whole 4 KiB blocks)
     int64_t total = 0;  // workgroups of the uniform launch
@@ -93,8 +102,6 @@ struct BsjPlan {
     bool share = false;
     void *stream = nullptr;  // the block-address stream (in the scratch)
 };
-bool bsj_eligible_public(const MatmulParams &p);
-size_t bsj_scratch_bytes_public(const MatmulParams &p, bool wide);
 hipError_t bsj_prepare(const MatmulParams &p, hipStream_t s, void *scratch, size_t scratch_bytes, bool share, bool wide,
                        BsjPlan &b);
 // The block-address stream of launch_matmul(p, v)'s bit-sliced product written ahead into buf (one offset launch on s),
@@ -109,7 +116,7 @@ hipError_t launch_bsj_stream(const MatmulParams &p, MatmulVariant v, hipStream_t
 // an upper bound of launch_bsj_stream's buffer for n_obj objects of n_out x n_in coefficients
 size_t bsj_stream_bytes_bound(int n_obj, int n_out, int n_in);
 
-// ---- ragged batches: one launch per kernel stage over objects of different shapes (wire.hip) -----------------
+// ---- ragged batches (ragged.hip): one launch per kernel stage over objects of different shapes (wire.hip) ------
 // One object's part of a ragged matmul launch (device-side descriptor table, 120 bytes).  Objects are ordered by
 // wg0 (and, in the block-address stream, by idx0).
 struct RaggedObj {
@@ -134,14 +141,13 @@ constexpr int kRaggedColBlock = 4096;  // columns per workgroup (both ragged ker
 bool ragged_bsj_eligible(const uint8_t *in, const uint8_t *out, int64_t in_row, int64_t out_row, int64_t width,
                          int n_out,
                          bool unaligned_ok);  // unaligned_ok: unaligned_vector_ok(), looked up once per call
-int ragged_bsj_waves(int n_out);  // 1, 2, 4 waves (8, 16, 32-row tiles) up to 32 output rows, else 8 (64-row tiles)
-// the shared program's block table address (probe_scratch: >= 8 device bytes; synchronous the first time)
-hipError_t ragged_bsj_base(hipStream_t s, void *probe_scratch, uint64_t &base);
+// (its waves: bsj_waves(n_out, true); the shared programs' block table: bsj_shared_base)
 hipError_t launch_ragged_offsets(const RaggedObj *objs, int n, int64_t entries, void *stream, uint64_t base,
                                  hipStream_t s);
 hipError_t launch_ragged_bsj(int W, const RaggedObj *objs, int n, int64_t wgs, const void *stream, hipStream_t s);
 hipError_t launch_ragged_perm(const RaggedObj *objs, int n, int64_t wgs, hipStream_t s);
 
+// ---- elementwise.hip ----
 // Element-wise primitives (src/common/simd/mod.rs:18-119) on one device vector.
 hipError_t launch_mul_vec_by_scalar(uint8_t *vec, int64_t len, uint8_t scalar, hipStream_t s);
 hipError_t launch_add_vectors(uint8_t *dst, const uint8_t *src, int64_t len, hipStream_t s);
@@ -154,88 +160,6 @@ hipError_t launch_mul_add(uint8_t *dst, const uint8_t *src, int64_t len, uint8_t
 // data[o][0:len); status[o] = 0 / invalid_code, final_len[o] = marker index (one launch, one wave per object).
 hipError_t launch_final_data_len(const uint8_t *data, int64_t obj_stride, int64_t len, int n_obj, int32_t *status,
                                  int64_t *final_len, int32_t invalid_code, hipStream_t s);
-
-// Device replica of Decoder::decode over pieces 0..m-1 of every object (rref.hip).  Piece p of object o
-// starts (coefficient header first) at pieces + o*obj_stride + p*piece_stride.  Outputs: status[o][p]
-// (RLNC status of each decode() call), rank[o], T[o] (k × m, row-major, rows >= rank zero).
-struct RrefParams {
-    const uint8_t *pieces;
-    int64_t obj_stride, piece_stride;
-    int k, m, n_obj;
-    uint8_t *T;
-    int64_t T_obj;
-    int32_t *status;
-    int32_t *rank;
-    int block_only;  // 1 = decode path 5: the blocked run (gf_rref_block_kernel), never the small-object kernel or the
-                     // two-pass split; 0 = chosen by shape (launch_rref_one)
-    const struct RrefObj *objs = nullptr;  // ragged batch: object o's shape and buffers (the fields above unused)
-    // two-pass elimination when k + m > 256 (k <= 128): pass 1 (the blocked run) replays only the first m pieces of
-    // each object with statuses / T at row stride m_stride (> m): an object full-ranked within them is exact
-    // (decode() answers ReceivedAllPieces for every later piece and leaves the state alone, decoder.rs:97-99); pass 2
-    // (the general kernel over all pieces) skips the objects pass 1 full-ranked (skip_full) and redoes the others
-    int m_stride = 0;   // 0 = m
-    int skip_full = 0;
-    // optional (the small-object kernel only): also write T as the 1- / 2-wave bit-sliced program's block-offset
-    // stream -- bsj_stream[o][j][i] = T[i][j] · bsj_block_bytes for i < bsj_tile_rows (0 past k) -- so the T × data
-    // product needs no offset launch (MatmulParams::bsj_stream); launch_rref_batch reports whether it did
-    uint32_t *bsj_stream = nullptr;
-    uint32_t bsj_block_bytes = 0;
-    int bsj_tile_rows = 0;
-    // optional, with bsj_stream (same kernel): get_final_data_len (decoder.rs:162-177) decided from the last 64
-    // payload bytes -- decoded row k - 1's last 64 bytes computed from T and the pieces' tails (tail_L = L, a multiple
-    // of 4, >= 64; k and the object stride multiples of 4): tail_status / tail_len the object's status and final length when its last
-    // nonzero byte lies there (or rank < k), else tail_need[o] = 1 (the product's workgroup scans the whole payload,
-    // MatmulParams::scan_need)
-    int32_t *tail_status = nullptr;
-    int64_t *tail_len = nullptr;
-    int32_t *tail_need = nullptr;
-    int64_t tail_L = 0;
-};
-// One object of a ragged elimination launch (rlnc_decode_ragged): T is k x m row-major, status m entries.
-struct RrefObj {
-    const uint8_t *pieces;
-    int64_t piece_stride;
-    uint8_t *T;
-    int32_t *status;
-    int32_t *rank;
-    int32_t k, m;      // m = received pieces (the row stride of T and of the statuses)
-    int32_t m_first;   // > 0: the blocked pass replays only the first m_first pieces (see RrefParams::m_stride)
-    int32_t two_pass;  // the general pass skips this object when the blocked pass full-ranked it
-};
-// ragged elimination: one workgroup per object of the device table objs (n objects, k + m <= 256 each when
-// block = true -- the blocked clean run -- else the one-wave LDS kernel); lds = the largest object's need
-size_t rref_block_lds_bytes_public(int k, int m);
-hipError_t launch_rref_ragged(const RrefObj *objs, int n, bool block, size_t lds, int hdr_lds, hipStream_t s);
-size_t rref_lds_bytes_staged_public(int k, int m);
-constexpr size_t kRrefMaxLds = 160 * 1024;
-// hipFuncAttributeMaxDynamicSharedMemorySize = kRrefMaxLds for a call site's kernels, set once per device (function
-// attributes are per device) under a lock: one static instance per call site, set() before the launch
-struct MaxLdsAttr {
-    std::mutex mu;
-    bool done[64] = {};
-    template <class... Kernels>
-    hipError_t set(Kernels... kernels) {
-        int dev = 0;
-        hipError_t e = hipGetDevice(&dev);
-        if (e != hipSuccess) return e;
-        if (dev < 0 || dev >= 64) return hipErrorInvalidDevice;
-        std::lock_guard<std::mutex> lock(mu);
-        if (done[dev]) return hipSuccess;
-        for (const void *f : {reinterpret_cast<const void *>(kernels)...}) {
-            e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, int(kRrefMaxLds));
-            if (e != hipSuccess) return e;
-        }
-        done[dev] = true;
-        return hipSuccess;
-    }
-};
-size_t rref_lds_bytes(int k, int m);
-// the blocked clean-run kernel (decode path 5, and what 0 / 2 pick) applies: a row fits one wave (k + m <= 256)
-bool rref_block_eligible(int k, int m);
-hipError_t launch_rref_batch(const RrefParams &p, hipStream_t s, bool *bsj_written = nullptr);
-// block bytes and tile rows of the unshared bit-sliced programs (for RrefParams::bsj_*): tile rows 0 = not one of them
-uint32_t bsj_block_bytes_public();
-int bsj_unshared_tile_rows(int n_out);
 
 // final_len with the decoder's rank: objects with rank < k report NotAllPiecesReceivedYet
 hipError_t launch_final_data_len_ranked(const uint8_t *data, int64_t obj_stride, int64_t len, int n_obj, int k,

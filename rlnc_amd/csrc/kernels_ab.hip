@@ -21,6 +21,41 @@ namespace rlnc {
 
 namespace {
 
+// The perm kernels' accumulator zeroing and table build as helpers, for the variants of this file only.
+// The shipped kernels (perm_kernels.hpp, ragged.hip) keep both written out, and their multiply too: called through a
+// __forceinline__ helper, the same statements compile to different loop bodies and register counts (the helper is
+// simplified on its own before it is inlined) -- measured per helper in profiles/r14_product_isa_identity.txt.
+template <int N>
+__device__ __forceinline__ void zero_acc(uint32_t (&acc)[N][4]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0u;
+}
+template <int N, int VW>
+__device__ __forceinline__ void zero_acc(uint32_t (&acc)[N][VW][4]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) zero_acc(acc[i]);
+}
+
+// the LDS tables of one coefficient chunk: s_t01[j][i] / s_t2[j][i] = make_perm_table(coef[i][j0 + j]) for the tile's
+// rows i < rows_here and the chunk's sources j < kc, the zero table elsewhere
+template <int NT>
+__device__ __forceinline__ void build_perm_tables(uint4 (*s_t01)[NT], uint32_t (*s_t2)[NT], const uint8_t *coef_base,
+                                                  int64_t coef_row, int rows_here, int j0, int kc) {
+    for (int e = threadIdx.x; e < kKC * NT; e += kThreads) {
+        const int i = e % NT, j = e / NT;
+        const uint8_t c = (i < rows_here && j < kc) ? coef_base[int64_t(i) * coef_row + j0 + j] : uint8_t(0);
+        const PermTable pt = make_perm_table(c);
+        s_t01[j][i] = make_uint4(pt.t0lo, pt.t0hi, pt.t1lo, pt.t1hi);
+        s_t2[j][i] = pt.t2;
+    }
+}
+
+// the columns [full, width) of a product, through the shipped perm path
+hipError_t tail_perm(const MatmulParams &p, int64_t full, hipStream_t s) {
+    if (full >= p.width) return hipSuccess;
+    return launch_matmul(tail_params(p, full), s, MatmulVariant::Perm);
+}
+
 // Wide variant: each lane owns VW 16-byte slots per source row (slot v at column v·4 KiB inside an
 // (VW·4 KiB) block), so every table read from LDS — the measured bottleneck of the VW = 1 kernel (a build
 // that reads one table set per source row ran 2.2× faster) — feeds VW× more multiply-adds.  Full aligned
@@ -40,21 +75,12 @@ __global__ __launch_bounds__(kThreads) void gf_matmul_wide_kernel(MatmulParams p
     const uint8_t *coef_base = p.coef + int64_t(obj) * p.coef_obj + int64_t(row0) * p.coef_row;
 
     uint32_t acc[NT][VW][4];
-#pragma unroll
-    for (int i = 0; i < NT; ++i)
-#pragma unroll
-        for (int v = 0; v < VW; ++v) acc[i][v][0] = acc[i][v][1] = acc[i][v][2] = acc[i][v][3] = 0u;
+    zero_acc(acc);
 
     for (int j0 = 0; j0 < p.n_in; j0 += kKC) {
         const int kc = min(kKC, p.n_in - j0);
         if (j0) __syncthreads();
-        for (int e = threadIdx.x; e < kKC * NT; e += kThreads) {
-            const int i = e % NT, j = e / NT;
-            const uint8_t c = (i < rows_here && j < kc) ? coef_base[int64_t(i) * p.coef_row + j0 + j] : uint8_t(0);
-            const PermTable pt = make_perm_table(c);
-            s_t01[j][i] = make_uint4(pt.t0lo, pt.t0hi, pt.t1lo, pt.t1hi);
-            s_t2[j][i] = pt.t2;
-        }
+        build_perm_tables<NT>(s_t01, s_t2, coef_base, p.coef_row, rows_here, j0, kc);
         __syncthreads();
         const uint8_t *rowp = in_base + int64_t(j0) * p.in_row;
         const uint4 zero = make_uint4(0, 0, 0, 0);
@@ -102,13 +128,7 @@ __global__ __launch_bounds__(kThreads) void gf_matmul_wide_kernel(MatmulParams p
             for (int v = 0; v < VW; ++v)
                 *reinterpret_cast<uint4 *>(out_base + int64_t(i) * p.out_row + v * kSlot) =
                     make_uint4(acc[i][v][0], acc[i][v][1], acc[i][v][2], acc[i][v][3]);
-    if (p.hdr != nullptr && cb == 0) {
-        uint8_t *h = p.hdr + int64_t(obj) * p.hdr_obj + int64_t(row0) * p.hdr_row;
-        for (int e = threadIdx.x; e < rows_here * p.n_in; e += kThreads) {
-            const int i = e / p.n_in, j = e % p.n_in;
-            h[int64_t(i) * p.hdr_row + j] = coef_base[int64_t(i) * p.coef_row + j];
-        }
-    }
+    if (p.hdr != nullptr && cb == 0) copy_header_rows(p, obj, row0, rows_here, kThreads);
 }
 
 // Three-source variant: the 24 bits of three source bytes (x, y, z) are cut into eight 3-bit chunks
@@ -213,8 +233,7 @@ __global__ __launch_bounds__(kThreads) void gf_matmul_perm3_kernel(MatmulParams 
     const uint8_t *coef_base = p.coef + int64_t(t.obj) * p.coef_obj + int64_t(t.row0) * p.coef_row;
 
     uint32_t acc[NT][4];
-#pragma unroll
-    for (int i = 0; i < NT; ++i) acc[i][0] = acc[i][1] = acc[i][2] = acc[i][3] = 0u;
+    zero_acc(acc);
 
     for (int j0 = 0; j0 < p.n_in; j0 += kKC3) {
         const int kc = min(kKC3, p.n_in - j0);
@@ -258,11 +277,7 @@ hipError_t launch_perm3(const MatmulParams &p, hipStream_t s, bool aligned) {
     if (full > 0)
         if (hipError_t e = launch_perm3_one<NT, true>(p, full, s); e != hipSuccess) return e;
     if (full == p.width) return hipSuccess;
-    MatmulParams t = p;
-    t.in = p.in + full;
-    t.out = p.out + full;
-    if (full > 0) t.hdr = nullptr;
-    return launch_perm3_one<NT, false>(t, p.width - full, s);
+    return launch_perm3_one<NT, false>(tail_params(p, full), p.width - full, s);
 }
 
 template <int NT, int VW>
@@ -286,13 +301,7 @@ hipError_t launch_wide_split(const MatmulParams &p, hipStream_t s) {
         hipError_t e = launch_wide<NT, VW>(p, full, s);
         if (e != hipSuccess) return e;
     }
-    if (full == p.width) return hipSuccess;
-    MatmulParams t = p;
-    t.in = p.in + full;
-    t.out = p.out + full;
-    t.width = p.width - full;
-    if (full > 0) t.hdr = nullptr;
-    return launch_matmul(t, s, MatmulVariant::Perm);
+    return tail_perm(p, full, s);
 }
 
 
@@ -343,14 +352,7 @@ __global__ __launch_bounds__(kThreads) void gf_matmul_bs_kernel(MatmulParams p, 
     decode_block(p.n_obj * row_tiles * col_blocks, row_tiles, col_blocks, rt, cb, obj);
     const int row0 = rt * kBsRows;
     const int rows = min(kBsRows, p.n_out - row0);
-    if (p.hdr != nullptr && cb == 0) {
-        Tile t;
-        t.obj = obj;
-        t.cb = 0;
-        t.row0 = row0;
-        t.rows_here = rows;
-        copy_header(p, t);
-    }
+    if (p.hdr != nullptr && cb == 0) copy_header_rows(p, obj, row0, rows, kThreads);
     const uint8_t *src = p.in + int64_t(obj) * p.in_obj + int64_t(cb) * kBsColBlock;
     uint8_t *dst = p.out + int64_t(obj) * p.out_obj + int64_t(row0) * p.out_row + int64_t(cb) * kBsColBlock;
     const uint32_t *idx = stream + (int64_t(obj) * row_tiles + rt) * p.n_in * (kBsRows * kBsRowDwords);
@@ -477,20 +479,9 @@ bool operands_aligned(const MatmulParams &p) {
            (p.n_out == 1 || al16(p.out_row)) && (p.n_obj == 1 || al16(p.out_obj));
 }
 
-// the columns [full, width) of a product, through the shipped perm path
-hipError_t tail_perm(const MatmulParams &p, int64_t full, hipStream_t s) {
-    if (full >= p.width) return hipSuccess;
-    MatmulParams t = p;
-    t.in = p.in + full;
-    t.out = p.out + full;
-    t.width = p.width - full;
-    t.hdr = nullptr;
-    return launch_matmul(t, s, MatmulVariant::Perm);
-}
-
 hipError_t launch_run(const MatmulParams &p, hipStream_t s, void *scratch, size_t scratch_bytes) {
     // shapes the run program does not take are variant 8's (stream kernel, realigned copies, <= 32-row tiles)
-    if (p.n_out <= 32 || !operands_aligned(p) || !bsj_eligible_public(p))
+    if (p.n_out <= 32 || !operands_aligned(p) || !bsj_eligible(p, true))
         return launch_matmul(p, s, MatmulVariant::BitSlicedJumpShared8, scratch, scratch_bytes);
     BsjPlan b;
     if (hipError_t e = bsj_prepare(p, s, scratch, scratch_bytes, true, true, b); e != hipSuccess) return e;
@@ -523,7 +514,7 @@ size_t matmul_scratch_bytes_ab(const MatmulParams &p, MatmulVariant v) {
     if (p.n_out <= 0 || p.n_in <= 0 || p.n_obj <= 0) return 0;
     if (v == MatmulVariant::BitSliced) return bs_eligible(p, operands_aligned(p)) ? bs_scratch_bytes(p) : 0;
     if (v == MatmulVariant::BitSlicedJumpRun)
-        return std::max(matmul_scratch_bytes(p, MatmulVariant::BitSlicedJumpShared8), bsj_scratch_bytes_public(p, true));
+        return std::max(matmul_scratch_bytes(p, MatmulVariant::BitSlicedJumpShared8), bsj_scratch_bytes(p, true));
     return 0;
 }
 

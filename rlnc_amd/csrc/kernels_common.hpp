@@ -1,6 +1,6 @@
-// kernels_common.hpp — device helpers shared by the matmul kernels of kernels.hip and the A/B variants of
-// kernels_ab.hip (internal to librlnc_hip): launch constants, the 3-bit-split v_perm multiply, 16-byte row access, the
-// XCD-aware work decode and the perm kernels' tile.
+// kernels_common.hpp — device helpers shared by the product kernels (perm_kernels.hpp, kernels.hip, ragged.hip,
+// elementwise.hip) and the A/B variants of kernels_ab.hip (internal to librlnc_hip): launch constants, the 3-bit-split
+// v_perm multiply, 16-byte row access, the XCD-aware work decode, the perm kernels' tile and the header copy.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -81,6 +81,8 @@ __device__ __forceinline__ Sel selectors(uint4 x) {
 // XCD-aware work decode (cdna_hip_programming.md §5.5 T1): blocks b and b+8 share an XCD, so give every
 // XCD a contiguous range of work items, ordered row-tile-fastest: the row tiles of one column block then
 // run on one XCD and re-read that block's source rows from its L2 instead of HBM.
+// (The index is xcd_work_index's, restated in 32 bits: written as a call of it, the compiler orders the prologue of
+// every uniform kernel differently, and written in this form xcd_work_index does the same to the ragged kernels.)
 __device__ __forceinline__ void decode_block(int total, int row_tiles, int col_blocks, int &rt, int &cb, int &obj) {
     int b = blockIdx.x;
     int w = b;
@@ -94,6 +96,13 @@ __device__ __forceinline__ void decode_block(int total, int row_tiles, int col_b
     obj = rest / col_blocks;
 }
 
+// ... as a global work index of a ragged launch: XCD b & 7 gets a contiguous range of the launch's work items
+__device__ __forceinline__ int64_t xcd_work_index(int64_t total) {
+    const int64_t b = blockIdx.x;
+    if ((total & 7) == 0) return (b & 7) * (total >> 3) + (b >> 3);
+    return b;
+}
+
 // Per-workgroup tile: column block cb of object obj, output rows [row0, row0 + rows_here).
 struct Tile {
     int row0, rows_here, obj, cb;
@@ -102,15 +111,22 @@ struct Tile {
 };
 
 template <int NT>
-__device__ __forceinline__ Tile make_tile(const MatmulParams &p, int row_tiles, int col_blocks) {
+__device__ __forceinline__ Tile make_tile_at(const MatmulParams &p, int rt, int cb, int obj = 0) {
     Tile t;
-    int rt;
-    decode_block(p.n_obj * row_tiles * col_blocks, row_tiles, col_blocks, rt, t.cb, t.obj);
+    t.obj = obj;
+    t.cb = cb;
     t.row0 = rt * NT;
     t.rows_here = min(NT, p.n_out - t.row0);
     t.col = int64_t(t.cb) * kColBlock + int64_t(threadIdx.x) * kBytesPerThread;
     t.nbytes = t.col < p.width ? int(min<int64_t>(kBytesPerThread, p.width - t.col)) : 0;
     return t;
+}
+
+template <int NT>
+__device__ __forceinline__ Tile make_tile(const MatmulParams &p, int row_tiles, int col_blocks) {
+    int rt, cb, obj;
+    decode_block(p.n_obj * row_tiles * col_blocks, row_tiles, col_blocks, rt, cb, obj);
+    return make_tile_at<NT>(p, rt, cb, obj);
 }
 
 // VEC: plain 16-byte vector access (no per-lane branches in the hot loop, so the prefetched loads stay in
@@ -139,14 +155,21 @@ __device__ __forceinline__ void store_tile(const MatmulParams &p, const Tile &t,
                       t.nbytes);
 }
 
-__device__ __forceinline__ void copy_header(const MatmulParams &p, const Tile &t) {
-    if (p.hdr == nullptr || t.cb != 0) return;
-    const uint8_t *coef_base = p.coef + int64_t(t.obj) * p.coef_obj + int64_t(t.row0) * p.coef_row;
-    uint8_t *h = p.hdr + int64_t(t.obj) * p.hdr_obj + int64_t(t.row0) * p.hdr_row;
-    for (int e = threadIdx.x; e < t.rows_here * p.n_in; e += kThreads) {
+// coded-piece header (encoder.rs:246-248): the coefficient rows [row0, row0 + rows_here) of object obj copied to
+// p.hdr (not null) by the workgroup's `threads` threads
+__device__ __forceinline__ void copy_header_rows(const MatmulParams &p, int obj, int row0, int rows_here, int threads) {
+    const uint8_t *coef_base = p.coef + int64_t(obj) * p.coef_obj + int64_t(row0) * p.coef_row;
+    uint8_t *h = p.hdr + int64_t(obj) * p.hdr_obj + int64_t(row0) * p.hdr_row;
+    for (int e = threadIdx.x; e < rows_here * p.n_in; e += threads) {
         const int i = e / p.n_in, j = e % p.n_in;
         h[int64_t(i) * p.hdr_row + j] = coef_base[int64_t(i) * p.coef_row + j];
     }
+}
+
+// ... by the workgroup of the object's first column block
+__device__ __forceinline__ void copy_header(const MatmulParams &p, const Tile &t) {
+    if (p.hdr == nullptr || t.cb != 0) return;
+    copy_header_rows(p, t.obj, t.row0, t.rows_here, kThreads);
 }
 
 typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
@@ -178,6 +201,16 @@ __device__ __forceinline__ Sel selectors64(uint4 x) {
     s.s2[2] = uint32_t(b6) & 0x03030303u;
     s.s2[3] = uint32_t(b6 >> 32) & 0x03030303u;
     return s;
+}
+
+// the columns [full, width) of a product whose first `full` columns another launch takes
+inline MatmulParams tail_params(const MatmulParams &p, int64_t full) {
+    MatmulParams t = p;
+    t.in = p.in + full;
+    t.out = p.out + full;
+    t.width = p.width - full;
+    if (full > 0) t.hdr = nullptr;  // the header rows were written by the first launch
+    return t;
 }
 
 inline bool al16(const void *ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15) == 0; }

@@ -1,6 +1,6 @@
 // objects.cpp — the object API of librlnc_hip: Encoder / Recoder / Decoder behind the C ABI of include/rlnc_hip.h.
 // Mirrors rlnc::full::{Encoder, Recoder, Decoder} (src/full/*.rs): same constructor validation order, same status for
-// every error, same getters.  All GF(2^8) byte work on pieces runs on the device (piece.hip, kernels.hip); the host
+// every error, same getters.  All GF(2^8) byte work on pieces runs on the device (piece.hip, kernels.hip, elementwise.hip); the host
 // only runs the k×(k+slots) coefficient elimination of the decoder (elimination.hpp).
 #include <memory>
 #include <new>

@@ -11,7 +11,7 @@
 //     the reference's `parallel` split-then-XOR-reduce (encoder.rs:175-222): a workgroup owns 1 KiB of columns (16
 //     bytes a lane), each of its W waves multiplies ceil(k / W) source rows and the W partial sums meet in LDS;
 //   * reads the coefficients where the host left them (pinned memory: no H2D copy before the launch), one per lane,
-//     and turns each lane's coefficient into its 3-bit-split v_perm tables (kernels.hip) in registers; the wave then
+//     and turns each lane's coefficient into its 3-bit-split v_perm tables (perm_kernels.hpp) in registers; the wave then
 //     broadcasts row j's tables with v_readlane (no LDS table stage, no barrier before the arithmetic);
 //   * writes the output rows into pinned host memory (no D2H copy after it) with write-through stores and, per chunk
 //     of workgroups, counts finished workgroups in device memory; the chunk's last one raises its host flag, so the

@@ -19,7 +19,7 @@
 // barrier (rank, pc), taken through readfirstlane.
 #include "../../include/rlnc_hip.h"
 #include "gf_perm.hpp"
-#include "kernels.hpp"
+#include "rref.hpp"
 #include "rank_kernels.hpp"
 
 namespace rlnc {

@@ -11,7 +11,7 @@
 
 #include <cstddef>
 
-#include "kernels.hpp"
+#include "rref.hpp"
 
 namespace rlnc {
 

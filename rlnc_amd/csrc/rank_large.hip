@@ -45,7 +45,7 @@
 
 #include "../../include/rlnc_hip.h"
 #include "gf_perm.hpp"
-#include "kernels.hpp"
+#include "rref.hpp"
 #include "rank_large_kernels.hpp"
 
 namespace rlnc {

@@ -11,7 +11,7 @@
 #include <cstddef>
 #include <cstdint>
 
-#include "kernels.hpp"
+#include "rref.hpp"
 
 namespace rlnc {
 

@@ -5,7 +5,7 @@
 
 #include "../../include/rlnc_hip.h"
 #include "gf_perm.hpp"
-#include "kernels.hpp"
+#include "rref.hpp"
 
 namespace rlnc {
 
@@ -1324,20 +1324,6 @@ __global__ __launch_bounds__(64 * NW) void gf_rref_block_kernel(RrefParams p) {
 }
 
 constexpr int kBlkNW = 4, kBlkB = 8;  // waves per object and pieces per block of the blocked run
-// The two LDS budgets below are also the paths' eligibility limits (rref_block_eligible, the staged-header test), which
-// callers and tests mirror, so they keep counting what the retired forms needed: X rows for 16-piece blocks (the kernel
-// uses the first kBlkB), and 2 KiB of partial sums behind the staged headers (unused).
-constexpr int kBlkXRows = 16;
-
-size_t rref_block_lds_bytes(int k, int m) {
-    const int D = rref_row_dwords(k, m);
-    return size_t(kTabEntries) * kTabDw * 4 + size_t(k + 1) * 4 * D + 4 * ((size_t(m) + 3) & ~size_t(3)) +
-           ((size_t(m) * ((k + 3) & ~3) + 15) & ~size_t(15)) + size_t(kBlkXRows) * D * 4 + 16;
-}
-
-inline size_t rref_lds_bytes_staged(int k, int m) {  // + the staged headers
-    return rref_lds_bytes(k, m) + ((size_t(k) * m + 15) & ~size_t(15)) + 2 * 4 * 64 * 4;
-}
 
 }  // namespace
 }  // namespace rlnc

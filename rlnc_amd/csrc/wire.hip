@@ -6,7 +6,7 @@
 //     socket or file ingestion produces them.  Each kernel stage is ONE launch over a device-side descriptor table
 //     (per wave class of the bit-sliced program), not one launch per object or per shape.
 // The coeffs ‖ data framing of a coded piece is written by the matmul kernels themselves (header copy), and the
-// decoder's marker scan by a kernel here / in kernels.hip.
+// decoder's marker scan by a kernel here / in elementwise.hip.
 #include <algorithm>
 
 #include "context.hpp"
@@ -197,16 +197,16 @@ int ragged_matmul(rlnc_context *ctx, const std::vector<MatmulJob> &jobs) {
     int st;
     if (any_bsj) {
         if ((st = ctx->grow(ctx->ws_idx, 512))) return st;
-        HIP_TRY(rlnc::ragged_bsj_base(ctx->stream, ctx->ws_idx.p, base));
+        HIP_TRY(rlnc::bsj_shared_base(ctx->stream, ctx->ws_idx.p, base));
     }
     for (const auto &j : jobs) {
         if (j.n_out <= 0 || j.n_in <= 0 || j.width <= 0) continue;
         int64_t full = 0;
         // (the 1- and 2-wave programs take block offsets, not addresses: no base needed)
-        if ((base != 0 || rlnc::ragged_bsj_waves(j.n_out) <= 2) &&
+        if ((base != 0 || rlnc::bsj_waves(j.n_out, true) <= 2) &&
             rlnc::ragged_bsj_eligible(j.in, j.out, j.in_row, j.out_row, j.width, j.n_out, uv)) {
             full = (j.width / rlnc::kRaggedColBlock) * rlnc::kRaggedColBlock;
-            const int W = rlnc::ragged_bsj_waves(j.n_out);
+            const int W = rlnc::bsj_waves(j.n_out, true);
             RaggedObj d{};
             d.in = j.in;
             d.coef = j.coef;
@@ -465,7 +465,7 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
                 }
             } else if (rlnc::rref_block_eligible(k, m)) {
                 blk.push_back(r);
-                lds_blk = std::max(lds_blk, rlnc::rref_block_lds_bytes_public(k, m));
+                lds_blk = std::max(lds_blk, rlnc::rref_block_lds_bytes(k, m));
             } else if (rlnc::rref_lds_bytes(k, m) <= rlnc::kRrefMaxLds) {
                 // k <= 128: the blocked run over the first 256 - k pieces, the general kernel only for an object
                 // that did not reach rank k within them (rref.hip launch_rref_batch, two passes)
@@ -473,10 +473,10 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
                     r.m_first = 256 - k;
                     r.two_pass = 1;
                     blk.push_back(r);
-                    lds_blk = std::max(lds_blk, rlnc::rref_block_lds_bytes_public(k, 256 - k));
+                    lds_blk = std::max(lds_blk, rlnc::rref_block_lds_bytes(k, 256 - k));
                 }
                 wide.push_back(r);
-                if (rlnc::rref_lds_bytes_staged_public(k, m) > rlnc::kRrefMaxLds) hdr_lds = 0;
+                if (rlnc::rref_lds_bytes_staged(k, m) > rlnc::kRrefMaxLds) hdr_lds = 0;
             } else {
                 host.push_back(i);
             }
@@ -486,7 +486,7 @@ int rlnc_decode_ragged(rlnc_context *ctx, const rlnc_decode_object_desc *objs, s
     }
     size_t lds_wide = 0;  // one wide object's headers not fitting beside its matrix: none are staged
     for (const auto &r : wide)
-        lds_wide = std::max(lds_wide, hdr_lds ? rlnc::rref_lds_bytes_staged_public(r.k, r.m) : rlnc::rref_lds_bytes(r.k, r.m));
+        lds_wide = std::max(lds_wide, hdr_lds ? rlnc::rref_lds_bytes_staged(r.k, r.m) : rlnc::rref_lds_bytes(r.k, r.m));
     if (!tr.empty()) {
         void *dt = nullptr;
         if ((st = upload_table(ctx, tr.data(), tr.size() * sizeof(rlnc::RrefObj), &dt))) return st;

@@ -1,4 +1,5 @@
 #!/usr/bin/env bash
+# Archived: last worked on commit b38c0b1; RLNC_NARROW was retired with the next one (the decided form is the only one).
 # Narrow-operand kernel A/B: the GPU tests (new kernel, default), then scripts/bench_configs.py with RLNC_NARROW=0
 # (round-1 perm path) / 1 (gf_matmul_narrow_kernel), interleaved; configs[3]'s recode carries a 64-byte tail.
 set -u

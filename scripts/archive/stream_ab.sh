@@ -1,4 +1,5 @@
 #!/usr/bin/env bash
+# Archived: last worked on commit b38c0b1; RLNC_STREAM_FORM was retired with the next one (the decided form is the only one).
 # A/B of the single-pass stream kernel forms (RLNC_STREAM_FORM, kernels.hip launch_stream): n = 1, 2, 3 coded
 # pieces per source pass, 32 objects x k = 32 x 1 MiB, two interleaved passes.  Output: gpurun_out/stream_ab.jsonl
 set -u

@@ -10,7 +10,7 @@ from oracle import np_oracle as npo
 from tests.gpu_util import np_matmul
 
 MUL = npo.mul_table()
-MAX_LDS = 160 * 1024  # kRrefMaxLds (kernels.hpp)
+MAX_LDS = 160 * 1024  # kRrefMaxLds (rref.hpp)
 
 
 # ---- rank_large.hip (rank_large_kernels.hpp) -------------------------------------------------------------------------

@@ -6,7 +6,8 @@ on both sides, a mask of the documented footprint); after the call the whole are
 equals the numpy / oracle image, every other byte still holds its prefill, and the inputs are byte-identical to their
 host copies.  tests/test_footprint_host.py shows on numpy images that the check reports a stray or missing byte.
 
-Which parametrisation reaches which program (rlnc_amd/csrc/kernels.hip, launch_matmul; on a device with unaligned vector
+Which parametrisation reaches which program (rlnc_amd/csrc/kernels.hip, launch_matmul; the perm, narrow, stream and
+nibble kernels themselves are in perm_kernels.hpp, the ragged ones in ragged.hip, the scan kernel in elementwise.hip; on a device with unaligned vector
 access, rlnc_device_unaligned_vector_access = 1, every operand counts as aligned, so the branch depends on the variant,
 n_out, n_in and the width alone; elsewhere the misaligned cases run the same branches on realigned scratch rows):
 

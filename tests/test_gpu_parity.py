@@ -153,6 +153,27 @@ def test_matmul_eight_wave_tiles(ctx, n_out, n_in, W, nobj):
         assert np.array_equal(got[o], np_matmul(coef[o], inp[o])), o
 
 
+# the stream kernels' forms for launches that fill the device (n_out <= 3, n_in <= 32, >= 1,024 workgroups; the other
+# suites stay below that and reach only the four-rows-in-flight form): an even block count takes two 4 KiB slots per
+# lane, an odd one falls back to one slot per lane, here with the ragged tail inside the launch
+@pytest.mark.parametrize("W", [1024 * 4096, 1025 * 4096 + 19])
+@pytest.mark.parametrize("n_out", [1, 3])
+def test_matmul_stream_full_grid(ctx, n_out, W):
+    from rlnc_amd import batch
+
+    rng = np.random.default_rng(n_out + W)
+    coef = rng.integers(1, 256, (1, n_out, 2), dtype=np.uint8)
+    inp = rng.integers(0, 256, (1, 2, W), dtype=np.uint8)
+    out = prefilled((1, n_out, W), n_out + W)
+    ctx.set_kernel_variant(8, 0)
+    try:
+        batch.matmul(dev(coef), dev(inp), out, ctx)
+        got = host(out)
+    finally:
+        ctx.set_kernel_variant(DEFAULT_VARIANT, 0)
+    assert np.array_equal(got[0], np_matmul(coef[0], inp[0]))
+
+
 # variant 9: column runs (a workgroup walks `run` column blocks with its source-row stream unbroken); forced run
 # lengths against ragged runs, fewer sources than the DMA depth (the stream crosses several tiles at once), source
 # counts off the 12-row unroll, partial row tiles and the ragged byte tail
