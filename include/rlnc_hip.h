@@ -58,12 +58,16 @@
  *     in an int32 device array, how many of each object are filled.  A push advances every object to that count
  *     (capped by m and by max_new pieces per object and call) and leaves exactly the state a fresh mode-1 decoder has
  *     after decode() of the same slots in order -- the same statuses, rank and T, however the pieces were split over
- *     pushes.  The kernels are those of decode paths 7 and 8 with the block taken per object from the state
- *     (rlnc_amd/csrc/rank_large.hip); k <= 4096, m <= 8192.  Not covered: the slot capacity m counts every arrival,
- *     useless ones included (a stream that may see many dependent pieces wants m well above k); small generations run
- *     these workspace kernels too, not the LDS kernel of paths 0 and 2; the reference rank mode has no stream form
- *     (a context in mode 0 is refused).  Measured on one MI355X (profiles/r12_decode_stream.jsonl): see DESIGN.md
- *     §4.2.4.
+ *     pushes.  A push has two forms (rlnc_set_stream_form).  The workspace form runs the kernels of decode paths 7
+ *     and 8 with the block taken per object from the state (rlnc_amd/csrc/rank_large.hip): k <= 4096, m <= 8192, one
+ *     latch launch and three launches per block of B <= 32 pieces.  The LDS form (rlnc_amd/csrc/rank_stream.hip) is one
+ *     launch per push, for the generations whose rows fit one workgroup's LDS -- the condition of "Rank mode" above,
+ *     rlnc_decode_stream_lds_fits: an object's rows and pivots come from the state into LDS, the per-piece loop of the
+ *     mode-1 LDS kernel runs over the new slots only, and the rows go back.  Both leave the same state, byte for byte
+ *     in everything a later call reads, so they may be mixed from push to push on one state buffer.  Not covered: the
+ *     slot capacity m counts every arrival, useless ones included (a stream that may see many dependent pieces wants
+ *     m well above k); the reference rank mode has no stream form (a context in mode 0 is refused).  Measured on one
+ *     MI355X (profiles/r12_decode_stream.jsonl, profiles/r14_stream_lds.jsonl): see DESIGN.md §4.2.4.
  *   - Sparse coding vectors.  The *_sparse calls take a coefficient matrix as two arrays with a fixed number w of
  *     entries per output row: idx int32 [obj][n_out][w], the source-row index of each entry, and val uint8
  *     [obj][n_out][w], its coefficient.  The dense row c they stand for is c[j] = XOR of val[t] over all t with
@@ -431,14 +435,41 @@ size_t rlnc_decode_stream_state_bytes(size_t k, size_t m, size_t num_objects);
  * limits; the decode path setting is irrelevant. */
 int rlnc_decode_stream_init(rlnc_context *ctx, void *state_dev, size_t state_bytes, size_t k, size_t m,
                             size_t num_objects);
+/* Which kernels rlnc_decode_stream_push runs on this context (per context, like rlnc_set_decode_path; any other value
+ * is RLNC_ERR_INVALID_ARGUMENT and leaves the form as it was):
+ *   RLNC_STREAM_FORM_WORKSPACE  the workspace form, every shape a stream takes: 1 + 3 * ceil(min(max_new, m) / B)
+ *                               launches, plus one when rank_dev or answered_dev is asked for.
+ *   RLNC_STREAM_FORM_LDS        the LDS form: one launch per push, rank_dev / answered_dev included; avail_dev is read
+ *                               once per object in that launch.  An object with nothing new has no byte of its state
+ *                               written.  A push of a shape for which rlnc_decode_stream_lds_fits is 0 returns
+ *                               RLNC_ERR_INVALID_ARGUMENT and names the limit (no silent fallback to the other form).
+ *   RLNC_STREAM_FORM_AUTO       the default: the LDS form for k <= 48 with m <= 64, the workspace form otherwise.  That
+ *                               is where the LDS form was faster on every measured line (1.3-4x; dense and density-4
+ *                               vectors, one push of everything down to one piece per push, 32 to 4,096 objects).
+ *                               From k = 64 up the workspace form wins pushes of many pieces (2.5x for one push of
+ *                               everything at k = 200) and the LDS form pushes of one to three (2-3x): a receiver
+ *                               of such generations that pushes piece by piece sets RLNC_STREAM_FORM_LDS itself.
+ *                               One MI355X, profiles/r14_stream_lds.jsonl, DESIGN.md §4.2.4.
+ * The state buffer, init, snapshot and rlnc_decode_stream_state_bytes are the same for all three, and the forms may
+ * alternate from push to push on one state buffer: the state after a push does not depend on the forms used so far. */
+#define RLNC_STREAM_FORM_AUTO 0
+#define RLNC_STREAM_FORM_WORKSPACE 1
+#define RLNC_STREAM_FORM_LDS 2
+int rlnc_set_stream_form(rlnc_context *ctx, int form);
+/* 1 when the LDS form takes generation size k with m piece slots: 8192 + 4*(k*D + 2*D + m*ceil(k/4) + m + 2*k +
+ * ceil(k/4)) <= 160 KiB with D = ceil(k/4) + ceil(m/4), the condition of the mode-1 LDS kernel ("Rank mode" above);
+ * k = 200 with m = 210 fits, and so does k = 4 with m = 8192 (rows of more than 256 dwords).  0 otherwise, and for
+ * k == 0 or m == 0.  Pure: needs no context and no GPU. */
+int rlnc_decode_stream_lds_fits(size_t k, size_t m);
 /* Object o advances from done_o, the slots answered so far, to min(max(avail_dev[o], done_o), m, done_o + max_new):
  * those slots of pieces_dev (addressed as in rlnc_decode_batch_eliminate: object stride in bytes, 0 = m*(k+L)) are
  * pushed to its decoder in order.  An avail below done_o changes nothing; one above m is clamped.  Asynchronous on
  * the context's stream, never synchronises and grows no context workspace, so it can be captured into a HIP graph
  * and replayed while avail_dev changes between replays.  avail_dev (int32 [num_objects]) is read by the call's first
- * launch only: the caller may overwrite it as soon as the call returns.  1 + 3 * ceil(min(max_new, m) / B) launches
- * (B <= 32 pieces per block), plus one when rank_dev or answered_dev (int32 [num_objects], each may be NULL) are
- * asked for: every object's rank and done_o after the push.  An object whose rank is k still consumes its slots
+ * launch only: the caller may overwrite it as soon as the call returns.  In the workspace form 1 + 3 *
+ * ceil(min(max_new, m) / B) launches (B <= 32 pieces per block), plus one when rank_dev or answered_dev (int32
+ * [num_objects], each may be NULL) are asked for: every object's rank and done_o after the push; in the LDS form one
+ * launch in all (rlnc_set_stream_form).  An object whose rank is k still consumes its slots
  * (ReceivedAllPieces).  k == 0 PieceCountZero, then L == 0 PieceLengthZero; max_new == 0 or num_objects == 0: RLNC_OK,
  * nothing launched. */
 int rlnc_decode_stream_push(rlnc_context *ctx, void *state_dev, size_t state_bytes, const uint8_t *pieces_dev,

@@ -67,6 +67,10 @@ RLNC_DECODE_PATH_DEVICE_ANY = 7
 RLNC_DECODE_PATH_LARGE = 8
 # a decode stream's slot that no push has answered yet (rlnc_decode_stream_snapshot)
 RLNC_STATUS_PENDING = -1
+# which kernels a decode stream's push runs (rlnc_set_stream_form)
+RLNC_STREAM_FORM_AUTO = 0
+RLNC_STREAM_FORM_WORKSPACE = 1
+RLNC_STREAM_FORM_LDS = 2
 
 _SIGS = {
     "rlnc_status_name": (C.c_char_p, [C.c_int]),
@@ -148,6 +152,8 @@ _SIGS = {
                                                   vp, vp, vp, vp, vp, vp]),
     "rlnc_decode_stream_state_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t]),
     "rlnc_decode_stream_init": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "rlnc_set_stream_form": (C.c_int, [vp, C.c_int]),
+    "rlnc_decode_stream_lds_fits": (C.c_int, [C.c_size_t, C.c_size_t]),
     "rlnc_decode_stream_push": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                           C.c_size_t, vp, C.c_size_t, vp, vp]),
     "rlnc_decode_stream_snapshot": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp]),

@@ -440,6 +440,14 @@ def state_bytes(k: int, m: int, num_objects: int) -> int:
     return int(load().rlnc_decode_stream_state_bytes(k, m, num_objects))
 
 
+def stream_lds_fits(k: int, m: int) -> bool:
+    """Whether the one-launch LDS form of a decode stream's push (Context.set_stream_form(2)) takes generation size k
+    with m piece slots: the LDS condition of the true-rank device kernel.  False for k = 0 or m = 0.  Needs no GPU."""
+    from ._lib import load
+
+    return bool(load().rlnc_decode_stream_lds_fits(k, m))
+
+
 class DecodeStream:
     """The true-rank decoder state of num_objects objects (generation size k, m piece slots each) kept on the device
     between calls.  Slot t of object o is pieces[o][t] of the caller's pieces [obj][m][k+L] tensor; the caller fills
@@ -447,7 +455,7 @@ class DecodeStream:
     After any sequence of pushes the state is a fresh mode-1 decoder's after decode() of the same slots in order.
 
     ctx: a context in rank mode 1 (a context in mode 0 is refused); None: a context of the stream's own, in rank mode 1
-    on torch's current device.  Every call launches on torch's current stream and none synchronises."""
+    on torch's current device.  push runs the form of that context (Context.set_stream_form).  Every call launches on torch's current stream and none synchronises."""
 
     def __init__(self, k: int, m: int, num_objects: int, ctx: Context | None = None):
         import torch

@@ -65,6 +65,14 @@ class Context:
         the decoders created on it afterwards.  In mode 1 decode path 5 is InvalidArgument, in mode 0 paths 7 and 8."""
         check(self.lib.rlnc_set_rank_mode(self.h, int(mode)), self.lib)
 
+    def set_stream_form(self, form: int = 0):
+        """Which kernels DecodeStream.push runs on this context: 1 (RLNC_STREAM_FORM_WORKSPACE) the workspace form,
+        every shape a stream takes; 2 (RLNC_STREAM_FORM_LDS) the one-launch LDS form, for the shapes of
+        batch.stream_lds_fits (a push of another shape is InvalidArgument, no silent fallback); 0 (default) the
+        measured choice between them: the LDS form for k <= 48 with m <= 64 (include/rlnc_hip.h, rlnc_set_stream_form).  The forms leave the same state and
+        may alternate from push to push.  Every other value is InvalidArgument and leaves the form as it was."""
+        check(self.lib.rlnc_set_stream_form(self.h, int(form)), self.lib)
+
     @property
     def rank_mode(self) -> int:
         return int(self.lib.rlnc_get_rank_mode(self.h))

@@ -247,6 +247,7 @@ struct rlnc_context {
                           // 5 blocked clean run, 7 device for every shape (rank mode 1: rank.hip where it fits LDS,
                           // rank_large.hip beyond), 8 rank_large.hip for every shape (3, 4, 6: retired, never set)
     int rank_mode = 0;  // RLNC_RANK_MODE_*: 0 the reference's diagonal-pivot replica, 1 true rank (rank.hip, elimination.hpp)
+    int stream_form = 0;  // RLNC_STREAM_FORM_*: which kernels rlnc_decode_stream_push runs (decode_stream.cpp)
     // the device elimination of this context's rank mode fits LDS
     bool elim_fits(size_t k, size_t m) const {
         return (rank_mode == RLNC_RANK_MODE_TRUE ? rlnc::rank_lds_bytes(int(k), int(m)) : rlnc::rref_lds_bytes(int(k), int(m))) <=

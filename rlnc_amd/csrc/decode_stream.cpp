@@ -1,11 +1,13 @@
 // decode_stream.cpp — the resumable device decode of librlnc_hip (include/rlnc_hip.h, "Decode streams"): the
 // true-rank decoder state of many objects in a caller-owned device buffer, pushed forward as pieces arrive
-// (rank_large.hip in its stream form; rank_large_kernels.hpp), and the registry of initialised state buffers.
+// (rank_large.hip in its stream form, rank_large_kernels.hpp; for generations that fit LDS also the one-launch form of
+// rank_stream.hip, rank_stream_kernels.hpp), and the registry of initialised state buffers.
 #include <mutex>
 #include <tuple>
 #include <vector>
 
 #include "context.hpp"
+#include "rank_stream_kernels.hpp"
 
 using namespace rlnc::eng;
 
@@ -63,9 +65,25 @@ int stream_args(rlnc_context *ctx, const void *state, size_t state_bytes, size_t
     return RLNC_OK;
 }
 
+// RLNC_STREAM_FORM_AUTO: the LDS form where it was measured faster than the workspace form by more than the two arms'
+// spread on every line -- dense and density-4 vectors, one push of everything down to one piece per push, 32 to 4,096
+// objects -- which is k <= 48 with m <= 64 (profiles/r14_stream_lds.jsonl).  From k = 64 on the
+// workspace form wins some or most lines with several pieces per push; the object count did not decide any line.
+constexpr size_t kStreamAutoLdsMaxK = 48, kStreamAutoLdsMaxM = 64;
+bool stream_auto_lds(size_t k, size_t m) { return k <= kStreamAutoLdsMaxK && m <= kStreamAutoLdsMaxM; }
+
 }  // namespace
 
 extern "C" {
+
+int rlnc_set_stream_form(rlnc_context *ctx, int form) {
+    CHECK_ARG(ctx != nullptr && (form == RLNC_STREAM_FORM_AUTO || form == RLNC_STREAM_FORM_WORKSPACE ||
+                                 form == RLNC_STREAM_FORM_LDS));
+    ctx->stream_form = form;
+    return RLNC_OK;
+}
+
+int rlnc_decode_stream_lds_fits(size_t k, size_t m) { return rlnc::rank_stream_lds_fits(k, m) ? 1 : 0; }
 
 size_t rlnc_decode_stream_state_bytes(size_t k, size_t m, size_t nobj) {
     return rlnc::rank_stream_state_bytes(k, m, nobj);
@@ -92,6 +110,14 @@ int rlnc_decode_stream_push(rlnc_context *ctx, void *state, size_t state_bytes, 
     if (obj_stride == 0) obj_stride = m * (k + L);
     CHECK_ARG(obj_stride >= m * (k + L));
     if ((st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
+    const bool fits = rlnc::rank_stream_lds_fits(k, m);
+    if (ctx->stream_form == RLNC_STREAM_FORM_LDS && !fits)  // no silent fallback to the workspace form
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "stream form %d (LDS) takes 8192 + 4*(k*D + 2*D + m*ceil(k/4) + m + 2*k + ceil(k/4)) <= %zu bytes, "
+                         "D = ceil(k/4) + ceil(m/4): k=%zu, m=%zu takes %zu (rlnc_set_stream_form)",
+                         RLNC_STREAM_FORM_LDS, rlnc::kRrefMaxLds, k, m, rlnc::rank_lds_bytes(int(k), int(m)));
+    const bool lds = ctx->stream_form == RLNC_STREAM_FORM_LDS ||
+                     (ctx->stream_form == RLNC_STREAM_FORM_AUTO && fits && stream_auto_lds(k, m));
     if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
     rlnc::RrefParams rp{};
     rp.pieces = pieces;
@@ -100,8 +126,12 @@ int rlnc_decode_stream_push(rlnc_context *ctx, void *state, size_t state_bytes, 
     rp.k = int(k);
     rp.m = int(m);
     rp.n_obj = int(nobj);
-    HIP_TRY(rlnc::launch_rank_stream_push(rp, state, state_bytes, avail, int(std::min(max_new, m)), rank_dev,
-                                          answered_dev, ctx->stream));
+    if (lds)
+        HIP_TRY(rlnc::launch_rank_stream_push_lds(rp, state, state_bytes, avail, int(std::min(max_new, m)), rank_dev,
+                                                  answered_dev, ctx->stream));
+    else
+        HIP_TRY(rlnc::launch_rank_stream_push(rp, state, state_bytes, avail, int(std::min(max_new, m)), rank_dev,
+                                              answered_dev, ctx->stream));
     return RLNC_OK;
 }
 

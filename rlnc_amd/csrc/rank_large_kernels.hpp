@@ -73,7 +73,8 @@ hipError_t launch_rank_large(const RrefParams &p, void *ws, size_t ws_bytes, hip
 // object's block is pieces done .. min(done + B, target) - 1, read from its state; an object with nothing left returns
 // at once -- and, when asked for, one launch that copies out every object's rank and done.  The state after a push is
 // the one-piece-at-a-time model's after the same pieces (rank_large.hip: the proof is per block and does not care
-// where a block starts), so it does not depend on how the pieces were split over pushes.
+// where a block starts), so it does not depend on how the pieces were split over pushes.  Generations that fit LDS have
+// a one-launch form of the push besides (rank_stream_kernels.hpp) on the same state buffer.
 inline size_t rank_stream_state_bytes(size_t k, size_t m, size_t nobj) { return rank_large_workspace_bytes(k, m, nobj); }
 // rank, answered and target of every object to 0 (one launch); hipErrorInvalidValue as launch_rank_large
 hipError_t launch_rank_stream_init(int k, int m, int n_obj, void *state, size_t state_bytes, hipStream_t s);

@@ -35,6 +35,10 @@ pub const RLNC_DECODE_PATH_DEVICE_ANY: c_int = 7;
 pub const RLNC_DECODE_PATH_LARGE: c_int = 8;
 // a decode stream's slot that no push has answered yet (rlnc_decode_stream_snapshot)
 pub const RLNC_STATUS_PENDING: c_int = -1;
+// which kernels a decode stream's push runs (rlnc_set_stream_form)
+pub const RLNC_STREAM_FORM_AUTO: c_int = 0;
+pub const RLNC_STREAM_FORM_WORKSPACE: c_int = 1;
+pub const RLNC_STREAM_FORM_LDS: c_int = 2;
 
 // ---- opaque handles ----
 #[repr(C)]
@@ -493,6 +497,8 @@ unsafe extern "C" {
         m: usize,
         num_objects: usize,
     ) -> c_int;
+    pub fn rlnc_set_stream_form(ctx: *mut rlnc_context, form: c_int) -> c_int;
+    pub fn rlnc_decode_stream_lds_fits(k: usize, m: usize) -> c_int;
     pub fn rlnc_decode_stream_push(
         ctx: *mut rlnc_context,
         state_dev: *mut c_void,
