@@ -64,10 +64,14 @@
  *     launch per push, for the generations whose rows fit one workgroup's LDS -- the condition of "Rank mode" above,
  *     rlnc_decode_stream_lds_fits: an object's rows and pivots come from the state into LDS, the per-piece loop of the
  *     mode-1 LDS kernel runs over the new slots only, and the rows go back.  Both leave the same state, byte for byte
- *     in everything a later call reads, so they may be mixed from push to push on one state buffer.  Not covered: the
- *     slot capacity m counts every arrival, useless ones included (a stream that may see many dependent pieces wants
- *     m well above k); the reference rank mode has no stream form (a context in mode 0 is refused).  Measured on one
- *     MI355X (profiles/r12_decode_stream.jsonl, profiles/r14_stream_lds.jsonl): see DESIGN.md §4.2.4.
+ *     in everything a later call reads, so they may be mixed from push to push on one state buffer.
+ *     rlnc_decode_stream_compact (rlnc_amd/csrc/rank_compact.hip) reclaims the slots of useless arrivals and retires
+ *     finished objects in place, on the device: the useful pieces move to the first slots, the columns of the stored
+ *     rows are renumbered to match, and the state is a fresh stream's after the kept pieces -- so m bounds the pieces
+ *     an object holds, not the arrivals it sees, and a place is reused while its neighbours go on.  Not covered: the
+ *     reference rank mode has no stream form (a context in mode 0 is refused).  Measured on one MI355X
+ *     (profiles/r12_decode_stream.jsonl, profiles/r14_stream_lds.jsonl, profiles/r16_stream_compact.jsonl): see
+ *     DESIGN.md §4.2.4.
  *   - Sparse coding vectors.  The *_sparse calls take a coefficient matrix as two arrays with a fixed number w of
  *     entries per output row: idx int32 [obj][n_out][w], the source-row index of each entry, and val uint8
  *     [obj][n_out][w], its coefficient.  The dense row c they stand for is c[j] = XOR of val[t] over all t with
@@ -475,6 +479,41 @@ int rlnc_decode_stream_lds_fits(size_t k, size_t m);
 int rlnc_decode_stream_push(rlnc_context *ctx, void *state_dev, size_t state_bytes, const uint8_t *pieces_dev,
                             size_t pieces_obj_stride, size_t k, size_t L, size_t m, size_t num_objects,
                             const int32_t *avail_dev, size_t max_new, int32_t *rank_dev, int32_t *answered_dev);
+/* Reclaims the slots of useless arrivals and retires objects in place, so that m bounds the pieces an object holds
+ * and not the arrivals it has seen, and a finished object's place takes the next generation while the others go on.
+ * rank, done_o and the statuses are taken as the last push left them: the caller orders the call after that push (the
+ * context's stream does).  Per object o:
+ *   retired  (retire_dev != NULL and retire_dev[o] != 0) the four state words become 0, as init leaves them; nothing
+ *            else of the object's state and no byte of its pieces is written; kept_dev[o][*] = -1, answered_dev[o] = 0.
+ *   else     let u_0 < u_1 < ... < u_{r-1} be the slots below done_o whose status is Ok (r = rank).  The piece in slot
+ *            u_j moves to slot j, all k + L bytes; byte j of every stored row's e part becomes the old byte u_j and the
+ *            bytes from r on 0; the statuses of slots 0 .. r - 1 become Ok; the state words become {r, r, r, r}.
+ *            kept_dev[o][j] = u_j for j < r and -1 from r on; answered_dev[o] = r, the slot the object's next arrival
+ *            goes into: the caller's avail restarts from there.
+ *   idle     an object that is not retired and has no useless slot below done_o (done_o == rank, 0 included): no byte
+ *            of its state or pieces is written; kept_dev (the identity below r) and answered_dev are.
+ * pieces_dev == NULL: only the state is compacted, L and the stride are ignored -- for callers that keep their pieces
+ * behind an indirection of their own and move them by kept_dev.
+ * Equivalence: after the call the live state -- state words 0 and 2, piv[0 .. rank), St[0 .. done), R[0 .. rank)[D] --
+ * holds exactly the bytes a freshly initialised stream of the same shape holds after one push of the kept pieces in
+ * order (a useless piece left a zero column of e in every stored row, and the stored rows are the unique reduced rows
+ * of the span, so nothing is eliminated again: the call renumbers columns).  Later pushes (either form, alternating
+ * freely), snapshot and apply need no change and answer as a decoder that had seen the kept pieces and then whatever is
+ * pushed next.
+ * Footprint.  Written: the four state words; St[0 .. r); the e part of the stored rows 0 .. r - 1, all ceil(m/4)
+ * dwords; the state's Q region (scratch: the list u); the pieces slots j < r with u_j != j; the outputs.  Never
+ * written: piv; the rows' coefficient part; rows and statuses at or beyond r; pieces slots at or beyond r; the bytes
+ * between m*(k+L) and the object stride; retire_dev.
+ * Four launches (three without pieces) on the context's stream, whichever push form wrote the state, every shape a
+ * stream takes; never synchronises and grows no context workspace, so (compact, push) is capturable as a linear
+ * graph.  The piece move takes 16-byte accesses at any byte address where rlnc_device_unaligned_vector_access is 1,
+ * single bytes otherwise.  Checks in the order of push: a null handle RLNC_ERR_INVALID_ARGUMENT; k == 0
+ * PieceCountZero; with pieces_dev, L == 0 PieceLengthZero; num_objects == 0 RLNC_OK, nothing launched; then the state
+ * and shape checks of push (rank mode 0, a buffer never initialised or initialised for another shape) and
+ * pieces_obj_stride (0 = m*(k+L)) >= m*(k+L): RLNC_ERR_INVALID_ARGUMENT, nothing written. */
+int rlnc_decode_stream_compact(rlnc_context *ctx, void *state_dev, size_t state_bytes, uint8_t *pieces_dev,
+                               size_t pieces_obj_stride, size_t k, size_t L, size_t m, size_t num_objects,
+                               const int32_t *retire_dev, int32_t *kept_dev, int32_t *answered_dev);
 /* What the stream holds now, in the layout of rlnc_decode_batch_eliminate (one launch; any output may be NULL; the
  * state is not modified and a later push continues from it): T_dev [obj][k][m], rows in pivot order, rows >= rank
  * and columns >= done_o zero; piece_status_dev [obj][m], the decoder's answer for the slots below done_o and

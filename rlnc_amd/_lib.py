@@ -156,6 +156,8 @@ _SIGS = {
     "rlnc_decode_stream_lds_fits": (C.c_int, [C.c_size_t, C.c_size_t]),
     "rlnc_decode_stream_push": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                           C.c_size_t, vp, C.c_size_t, vp, vp]),
+    "rlnc_decode_stream_compact": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                             C.c_size_t, vp, vp, vp]),
     "rlnc_decode_stream_snapshot": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp]),
     "rlnc_recode_batch": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "rlnc_encode_batch_sparse": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t,

@@ -507,6 +507,24 @@ class DecodeStream:
                                             C.c_void_p(pieces.data_ptr()), obj_stride, self.k, L, self.m,
                                             self.num_objects, av, max_new, rk, an), c.lib)
 
+    def compact(self, pieces=None, retire=None, kept=None, answered=None) -> None:
+        """Reclaims the slots of useless arrivals and retires objects in place (rlnc_decode_stream_compact), after the
+        last push.  Object o with retire[o] != 0 (int32 [obj], optional) restarts empty: a new generation may be
+        written into its slots.  Every other object keeps the slots below done_o whose status is Ok, u_0 < ... <
+        u_{r-1}: piece u_j moves to slot j (pieces=None: only the state is compacted, the caller moves its pieces by
+        `kept`), and the stream is a fresh stream's after a push of the kept pieces.  kept (int32 [obj][k], optional)
+        receives u (-1 from r on, and for a retired object); answered (int32 [obj], optional) r, the slot of the
+        object's next arrival, 0 for a retired object: avail restarts from there."""
+        L, obj_stride = self._pieces(pieces) if pieces is not None else (0, 0)
+        n = (self.num_objects,)
+        rt = self._i32(retire, n, "retire") if retire is not None else None
+        kp = self._i32(kept, (self.num_objects, self.k), "kept") if kept is not None else None
+        an = self._i32(answered, n, "answered") if answered is not None else None
+        c = _ctx_for(self.state, self.ctx)
+        check(c.lib.rlnc_decode_stream_compact(c.h, C.c_void_p(self.state.data_ptr()), self.state.numel(),
+                                               C.c_void_p(pieces.data_ptr()) if pieces is not None else None,
+                                               obj_stride, self.k, L, self.m, self.num_objects, rt, kp, an), c.lib)
+
     def snapshot(self, T=None, piece_status=None, rank=None) -> None:
         """What the stream holds now (each output optional; the state is not modified): T uint8 [obj][k][m] as
         decode_batch_eliminate writes it (columns >= done_o zero), piece_status int32 [obj][m] (RLNC_STATUS_PENDING,

@@ -1,12 +1,14 @@
 // decode_stream.cpp — the resumable device decode of librlnc_hip (include/rlnc_hip.h, "Decode streams"): the
 // true-rank decoder state of many objects in a caller-owned device buffer, pushed forward as pieces arrive
 // (rank_large.hip in its stream form, rank_large_kernels.hpp; for generations that fit LDS also the one-launch form of
-// rank_stream.hip, rank_stream_kernels.hpp), and the registry of initialised state buffers.
+// rank_stream.hip, rank_stream_kernels.hpp), compacted in place (rank_compact.hip, rank_compact_kernels.hpp), and the
+// registry of initialised state buffers.
 #include <mutex>
 #include <tuple>
 #include <vector>
 
 #include "context.hpp"
+#include "rank_compact_kernels.hpp"
 #include "rank_stream_kernels.hpp"
 
 using namespace rlnc::eng;
@@ -132,6 +134,33 @@ int rlnc_decode_stream_push(rlnc_context *ctx, void *state, size_t state_bytes, 
     else
         HIP_TRY(rlnc::launch_rank_stream_push(rp, state, state_bytes, avail, int(std::min(max_new, m)), rank_dev,
                                               answered_dev, ctx->stream));
+    return RLNC_OK;
+}
+
+int rlnc_decode_stream_compact(rlnc_context *ctx, void *state, size_t state_bytes, uint8_t *pieces, size_t obj_stride,
+                               size_t k, size_t L, size_t m, size_t nobj, const int32_t *retire, int32_t *kept_dev,
+                               int32_t *answered_dev) {
+    CHECK_ARG(ctx != nullptr);
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    if (pieces != nullptr && L == 0) return RLNC_ERR_PIECE_LENGTH_ZERO;
+    if (nobj == 0) return RLNC_OK;
+    int st = stream_args(ctx, state, state_bytes, k, m, nobj);
+    if (st) return st;
+    rlnc::RrefParams rp{};
+    if (pieces != nullptr) {
+        CHECK_ARG(L <= (size_t(1) << 40));  // m * (k + L) stays far inside 64 bits
+        if (obj_stride == 0) obj_stride = m * (k + L);
+        CHECK_ARG(obj_stride >= m * (k + L));
+        rp.obj_stride = int64_t(obj_stride);
+        rp.piece_stride = int64_t(k + L);
+    }
+    if ((st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
+    if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
+    rp.k = int(k);
+    rp.m = int(m);
+    rp.n_obj = int(nobj);
+    HIP_TRY(rlnc::launch_rank_stream_compact(rp, pieces, state, state_bytes, retire, kept_dev, answered_dev,
+                                             rlnc::unaligned_vector_ok(), ctx->stream));
     return RLNC_OK;
 }
 

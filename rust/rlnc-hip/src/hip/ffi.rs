@@ -514,6 +514,20 @@ unsafe extern "C" {
         rank_dev: *mut i32,
         answered_dev: *mut i32,
     ) -> c_int;
+    pub fn rlnc_decode_stream_compact(
+        ctx: *mut rlnc_context,
+        state_dev: *mut c_void,
+        state_bytes: usize,
+        pieces_dev: *mut u8,
+        pieces_obj_stride: usize,
+        k: usize,
+        L: usize,
+        m: usize,
+        num_objects: usize,
+        retire_dev: *const i32,
+        kept_dev: *mut i32,
+        answered_dev: *mut i32,
+    ) -> c_int;
     pub fn rlnc_decode_stream_snapshot(
         ctx: *mut rlnc_context,
         state_dev: *const c_void,
