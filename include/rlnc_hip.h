@@ -64,7 +64,8 @@
  *     launch per push, for the generations whose rows fit one workgroup's LDS -- the condition of "Rank mode" above,
  *     rlnc_decode_stream_lds_fits: an object's rows and pivots come from the state into LDS, the per-piece loop of the
  *     mode-1 LDS kernel runs over the new slots only, and the rows go back.  Both leave the same state, byte for byte
- *     in everything a later call reads, so they may be mixed from push to push on one state buffer.
+ *     in everything a later call reads, so they may be mixed from push to push on one state buffer (its layout and
+ *     state words: rlnc_amd/csrc/rank_state.hpp).
  *     rlnc_decode_stream_compact (rlnc_amd/csrc/rank_compact.hip) reclaims the slots of useless arrivals and retires
  *     finished objects in place, on the device: the useful pieces move to the first slots, the columns of the stored
  *     rows are renumbered to match, and the state is a fresh stream's after the kept pieces -- so m bounds the pieces

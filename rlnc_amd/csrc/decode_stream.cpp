@@ -2,7 +2,7 @@
 // true-rank decoder state of many objects in a caller-owned device buffer, pushed forward as pieces arrive
 // (rank_large.hip in its stream form, rank_large_kernels.hpp; for generations that fit LDS also the one-launch form of
 // rank_stream.hip, rank_stream_kernels.hpp), compacted in place (rank_compact.hip, rank_compact_kernels.hpp), and the
-// registry of initialised state buffers.
+// registry of initialised state buffers.  The state buffer itself: rank_state.hpp.
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -67,6 +67,13 @@ int stream_args(rlnc_context *ctx, const void *state, size_t state_bytes, size_t
     return RLNC_OK;
 }
 
+// the shape of a stream call, as every launch on the state takes it (no pieces, no strides)
+rlnc::RrefParams stream_shape(size_t k, size_t m, size_t nobj) {
+    rlnc::RrefParams rp{};
+    rp.k = int(k), rp.m = int(m), rp.n_obj = int(nobj);
+    return rp;
+}
+
 // RLNC_STREAM_FORM_AUTO: the LDS form where it was measured faster than the workspace form by more than the two arms'
 // spread on every line -- dense and density-4 vectors, one push of everything down to one piece per push, 32 to 4,096
 // objects -- which is k <= 48 with m <= 64 (profiles/r14_stream_lds.jsonl).  From k = 64 on the
@@ -121,13 +128,10 @@ int rlnc_decode_stream_push(rlnc_context *ctx, void *state, size_t state_bytes, 
     const bool lds = ctx->stream_form == RLNC_STREAM_FORM_LDS ||
                      (ctx->stream_form == RLNC_STREAM_FORM_AUTO && fits && stream_auto_lds(k, m));
     if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
-    rlnc::RrefParams rp{};
+    rlnc::RrefParams rp = stream_shape(k, m, nobj);
     rp.pieces = pieces;
     rp.obj_stride = int64_t(obj_stride);
     rp.piece_stride = int64_t(k + L);
-    rp.k = int(k);
-    rp.m = int(m);
-    rp.n_obj = int(nobj);
     if (lds)
         HIP_TRY(rlnc::launch_rank_stream_push_lds(rp, state, state_bytes, avail, int(std::min(max_new, m)), rank_dev,
                                                   answered_dev, ctx->stream));
@@ -146,7 +150,7 @@ int rlnc_decode_stream_compact(rlnc_context *ctx, void *state, size_t state_byte
     if (nobj == 0) return RLNC_OK;
     int st = stream_args(ctx, state, state_bytes, k, m, nobj);
     if (st) return st;
-    rlnc::RrefParams rp{};
+    rlnc::RrefParams rp = stream_shape(k, m, nobj);
     if (pieces != nullptr) {
         CHECK_ARG(L <= (size_t(1) << 40));  // m * (k + L) stays far inside 64 bits
         if (obj_stride == 0) obj_stride = m * (k + L);
@@ -156,9 +160,6 @@ int rlnc_decode_stream_compact(rlnc_context *ctx, void *state, size_t state_byte
     }
     if ((st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
     if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
-    rp.k = int(k);
-    rp.m = int(m);
-    rp.n_obj = int(nobj);
     HIP_TRY(rlnc::launch_rank_stream_compact(rp, pieces, state, state_bytes, retire, kept_dev, answered_dev,
                                              rlnc::unaligned_vector_ok(), ctx->stream));
     return RLNC_OK;
@@ -169,10 +170,7 @@ int rlnc_decode_stream_snapshot(rlnc_context *ctx, const void *state, size_t sta
     int st = stream_args(ctx, state, state_bytes, k, m, nobj);
     if (st || (st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
     if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
-    rlnc::RrefParams rp{};
-    rp.k = int(k);
-    rp.m = int(m);
-    rp.n_obj = int(nobj);
+    rlnc::RrefParams rp = stream_shape(k, m, nobj);
     rp.T = T_dev;
     rp.T_obj = int64_t(k * m);
     rp.status = piece_status_dev;

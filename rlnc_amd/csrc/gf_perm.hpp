@@ -17,6 +17,7 @@ constexpr int kTabDw = 8;  // dwords per multiplier: t0lo t0hi t1lo t1hi t2 inv 
 // c^-1 = c^254 in dword 5; entry 256 + c = the layout of c^-1 (0 for c = 0), so that "multiply by the
 // inverse of the pivot" is one table read (the register path's normalisation).
 constexpr int kTabEntries = 512;
+constexpr int kMulTabDw = 256 * kTabDw;  // the multipliers 0..255 alone (8 KiB): what copy_table brings into LDS
 struct RrefTable {
     uint32_t v[kTabEntries * kTabDw];
 };

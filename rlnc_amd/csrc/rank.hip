@@ -26,8 +26,6 @@ namespace rlnc {
 
 namespace {
 
-constexpr int kRankTabDw = 256 * kTabDw;  // the multipliers 0..255 of kRrefTable (8 KiB)
-
 __host__ __device__ inline int rank_row_dwords(int k, int m) { return ((k + 3) >> 2) + ((m + 3) >> 2); }
 // dwords of one object's LDS region (rank_kernels.hpp), a multiple of 4
 __host__ __device__ inline size_t rank_obj_dwords(int k, int m) {
@@ -60,7 +58,7 @@ __global__ __launch_bounds__(256) void gf_true_rank_kernel(RrefParams p) {
     }
     const int k = p.k, m = p.m;
     const int kd = (k + 3) >> 2, D = rank_row_dwords(k, m);
-    uint32_t *rows = lds + kRankTabDw + size_t(int(threadIdx.x) / TPO) * rank_obj_dwords(k, m);
+    uint32_t *rows = lds + kMulTabDw + size_t(int(threadIdx.x) / TPO) * rank_obj_dwords(k, m);
     uint8_t *rowsB = reinterpret_cast<uint8_t *>(rows);
     uint32_t *vb = rows + k * D;  // two scratch rows, alternating by piece
     uint32_t *Hw = vb + 2 * D;    // m headers of kd dwords (bytes past k zero)
@@ -205,7 +203,7 @@ hipError_t rank_attr() {
 
 }  // namespace
 
-size_t rank_lds_bytes(int k, int m) { return size_t(kRankTabDw) * 4 + rank_obj_dwords(k, m) * 4; }
+size_t rank_lds_bytes(int k, int m) { return size_t(kMulTabDw) * 4 + rank_obj_dwords(k, m) * 4; }
 
 hipError_t launch_rank_batch(const RrefParams &p, hipStream_t s) {
     if (p.n_obj <= 0) return hipSuccess;
@@ -214,7 +212,7 @@ hipError_t launch_rank_batch(const RrefParams &p, hipStream_t s) {
     if (lds > kRrefMaxLds) return hipErrorInvalidValue;
     // many small objects: a workgroup per object leaves most of its lanes idle and the grid launch-bound
     if (p.k <= 16 && rank_row_dwords(p.k, p.m) <= 16 && p.n_obj >= 1024) {
-        const size_t lds4 = size_t(kRankTabDw) * 4 + 4 * rank_obj_dwords(p.k, p.m) * 4;  // < 20 KiB
+        const size_t lds4 = size_t(kMulTabDw) * 4 + 4 * rank_obj_dwords(p.k, p.m) * 4;  // < 20 KiB
         hipLaunchKernelGGL(gf_true_rank_kernel<64>, dim3((p.n_obj + 3) / 4), dim3(256), lds4, s, p);
         return hipGetLastError();
     }

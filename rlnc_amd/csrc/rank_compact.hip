@@ -1,7 +1,7 @@
 // rank_compact.hip — a decode stream's compaction (include/rlnc_hip.h, rlnc_decode_stream_compact; interface and the
-// equivalence argument: rank_compact_kernels.hpp; the state buffer: rank_large_kernels.hpp).
+// equivalence argument: rank_compact_kernels.hpp; the state buffer, its words and their protocol: rank_state.hpp).
 //
-// Per object the call reads rank and done (state words 0 and 2) as the last push left them, and the retire flag:
+// Per object the call reads rank and done (kStRank, kStDone) as the last push left them, and the retire flag:
 //   retired    retire[o] != 0: the four state words become 0; nothing else of the object is written;
 //   idle       done == rank (every slot below done is Ok, or done = 0): nothing of the object is written;
 //   active     done > rank: u_0 < ... < u_{r-1}, r = rank, are the slots below done with status Ok.  Byte j of every
@@ -27,10 +27,8 @@
 //           unaligned_vector_access), the last lane of a piece byte by byte; otherwise every lane owns 16 single
 //           bytes, 256 apart.  Ownership is by bytes in both: no access is wider than what the thread owns.
 //   commit  (one workgroup per object) St[0 .. r) = Ok, the state words, answered.
-// No launch reads St or the state words while a workgroup of the same launch writes them: only commit writes them, and
-// there each object's only reader is its own workgroup, whose reads come before the barrier that precedes the writes.
-// rows and move both read the list that plan wrote and write disjoint memory (rows of R; pieces), so they are
-// independent of each other.
+// Only commit writes St and the state words, each object's own workgroup behind its barrier (rank_state.hpp).  rows and
+// move both read the list that plan wrote and write disjoint memory (rows of R; pieces): they are independent.
 //
 // Rules kept by every kernel (rank_large.hip): no workgroup waits for another; every branch around a barrier is
 // workgroup-uniform, on values passed through readfirstlane; early returns come before any barrier; shared global
@@ -65,8 +63,8 @@ enum class Obj { Retired, Bad, Idle, Active };
 // what the call does with object o, from its state words and the retire flag; workgroup-uniform.  No launch but commit
 // writes either, and commit calls this before its barrier.
 __device__ __forceinline__ Obj classify(const CompactParams &p, const uint32_t *ws, int o, int &rank, int &done) {
-    rank = __builtin_amdgcn_readfirstlane(int(ws[0]));
-    done = __builtin_amdgcn_readfirstlane(int(ws[2]));
+    rank = __builtin_amdgcn_readfirstlane(int(ws[kStRank]));
+    done = __builtin_amdgcn_readfirstlane(int(ws[kStDone]));
     const int ret = p.retire != nullptr ? __builtin_amdgcn_readfirstlane(p.retire[o]) : 0;
     if (ret != 0) return Obj::Retired;
     if (rank < 0 || rank > p.k || done < rank || done > p.m) return Obj::Bad;
@@ -229,7 +227,7 @@ __global__ __launch_bounds__(256) void gf_stream_compact_commit(CompactParams p)
     int32_t *St = reinterpret_cast<int32_t *>(ws + p.off_st);
     for (int t = tid; t < r; t += 256) St[t] = RLNC_OK;
     if (tid == 0) {
-        *reinterpret_cast<uint4 *>(ws) = make_uint4(uint32_t(r), uint32_t(r), uint32_t(r), uint32_t(r));
+        store_state(ws, r, r);
         if (p.answered != nullptr) p.answered[o] = r;
     }
 }
@@ -240,9 +238,7 @@ hipError_t launch_rank_stream_compact(const RrefParams &rp, uint8_t *pieces, voi
                                       const int32_t *retire, int32_t *kept, int32_t *answered, bool vec16,
                                       hipStream_t s) {
     if (rp.n_obj <= 0) return hipSuccess;
-    if (rp.objs != nullptr || rp.k <= 0 || rp.m <= 0) return hipErrorInvalidValue;
-    const size_t need = rank_stream_state_bytes(size_t(rp.k), size_t(rp.m), size_t(rp.n_obj));
-    if (need == 0 || state == nullptr || (reinterpret_cast<uintptr_t>(state) & 15) != 0 || state_bytes < need)
+    if (rp.objs != nullptr || rank_state_check(rp.k, rp.m, rp.n_obj, state, state_bytes) != hipSuccess)
         return hipErrorInvalidValue;
     const LargeLayout L = large_layout(rp.k, rp.m);
     CompactParams p{};

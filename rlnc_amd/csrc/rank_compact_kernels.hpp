@@ -6,14 +6,14 @@
 // become 0).  Nothing is eliminated again: a useless piece was discarded by the elimination, so its column of e is zero
 // in every stored row, and the stored rows are the unique reduced rows of the span (rank_large.hip's proof); the state
 // after the slots 0 .. done - 1 is therefore a fresh stream's state after the useful slots alone, up to the renumbering
-// of the e columns that this call performs.  The state buffer and its layout: rank_large_kernels.hpp.
+// of the e columns that this call performs.  The state buffer and its words: rank_state.hpp.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
 #include <cstdint>
 
-#include "rank_large_kernels.hpp"
+#include "rank_state.hpp"
 #include "rref.hpp"
 
 namespace rlnc {

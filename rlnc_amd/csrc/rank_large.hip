@@ -1,11 +1,12 @@
 // rank_large.hip — the true-rank elimination for generations whose [coeffs | E] matrix does not fit one workgroup's LDS
-// (decode paths 7 and 8; semantics: include/rlnc_hip.h, "Rank mode"; interface and limits: rank_large_kernels.hpp).
+// (decode paths 7 and 8; semantics: include/rlnc_hip.h, "Rank mode"; interface: rank_large_kernels.hpp; the limits, the
+// layout and the state words with their protocol: rank_state.hpp).
 //
 // Per object the state lives in a device workspace: the stored rows R[rank][D] in arrival order (D = ceil(k/4) +
-// ceil(m/4) dwords, [c | e] as in rank.hip), their pivot columns piv[], the statuses St[], and {rank, rank before the
-// last block, pieces answered}.  The pieces are taken B at a time (large_block); every row operation is independent
-// per column, only the decisions read particular columns, so a block is three launches with no waiting between
-// workgroups -- the order between them is the stream's:
+// ceil(m/4) dwords, [c | e] as in rank.hip), their pivot columns piv[], the statuses St[], and the four state words.
+// The pieces are taken B at a time (large_block); every row operation is independent per column, only the decisions
+// read particular columns, so a block is three launches with no waiting between workgroups -- the order between them
+// is the stream's:
 //   reduce  (object x 64-dword column chunk; 4 waves = 4 groups of the block's pieces, piece t = 4j + wave)
 //           X_t = [h_t | unit(t)] ^ XOR_{i < rank} h_t[piv_i] · R_i.  The quotients are bytes of the headers themselves:
 //           R is a reduced row-echelon form, so row i is the only stored row with a nonzero byte in column piv_i.
@@ -30,13 +31,11 @@
 // and 0 in the rest of P, which determines it within the span: the state is the model's state after the same pieces.
 //
 // The stream form (template parameter STREAM; decode streams, rank_large_kernels.hpp): the state outlives the call, and
-// a block is each object's own -- t0 = pieces answered, b = min(B, target - t0), read from the state, where a latch
-// launch at the start of a push left the target.  The proof above is per block and does not say where a block starts,
-// so it holds for these blocks as it stands.  What differs from the one-shot form: an object with b = 0 is idle (every
-// workgroup of it returns before any barrier; its step still sets "rank before" to the rank, or the update would apply
-// the previous block's Q and new rows again), and an object at rank k still has its slots answered by the step
-// (ReceivedAllPieces, pieces answered += b), because the snapshot tells answered slots from pending ones.  The one-shot
-// instantiations keep the instructions they had before the parameter existed.
+// a block is each object's own, read from its state words (rank_state.hpp).  The proof above is per block and does not
+// say where a block starts, so it holds for these blocks as it stands.  What differs from the one-shot form: an object
+// with b = 0 is idle (every workgroup of it returns before any barrier), and an object at rank k still has its slots
+// answered by the step (ReceivedAllPieces, done += b), because the snapshot tells answered slots from pending ones.
+// The one-shot instantiations keep the instructions they had before the parameter existed.
 //
 // Rules kept by every kernel: no workgroup waits for another; every branch around a barrier is workgroup-uniform, on
 // values read after the previous barrier and passed through readfirstlane; the early return (nothing left to do) comes
@@ -52,7 +51,6 @@ namespace rlnc {
 
 namespace {
 
-constexpr int kTabDwords = 256 * kTabDw;  // the multipliers 0..255 of kRrefTable (8 KiB)
 constexpr int kColChunk = 64;             // dwords of a row per workgroup of the reduce and update grids
 constexpr int kQTile = 256;               // stored rows whose quotients the reduce stages at a time (a multiple of 64)
 constexpr int kUpdRows = 64;              // stored rows per workgroup of the update grid
@@ -74,18 +72,17 @@ struct LargeParams {
     int chunks, row_chunks, fin_chunks;
 };
 
-// The stream form of a block (STREAM kernels; rank_large_kernels.hpp, "Decode streams"): the object's own block, from
-// its state instead of the launch's t0 and b -- pieces done .. min(done + B, target) - 1, where the push's latch launch
-// left the target in the state's fourth word.  b <= 0: the object is idle in this block.  Both values are
-// workgroup-uniform: no launch that calls this writes words 2 and 3 before a barrier that follows the call.
+// The stream form of a block (STREAM kernels): the object's own block, from its state instead of the launch's t0 and
+// b -- pieces done .. min(done + B, target) - 1.  b <= 0: the object is idle in this block.  Both values are
+// workgroup-uniform: no launch that calls this writes kStDone or kStTarget before a barrier that follows the call.
 __device__ __forceinline__ void stream_block(const uint32_t *ws, int B, int &t0, int &b) {
-    t0 = __builtin_amdgcn_readfirstlane(int(ws[2]));
-    b = min(B, __builtin_amdgcn_readfirstlane(int(ws[3])) - t0);
+    t0 = __builtin_amdgcn_readfirstlane(int(ws[kStDone]));
+    b = min(B, __builtin_amdgcn_readfirstlane(int(ws[kStTarget])) - t0);
 }
 
 template <bool STREAM>
 __global__ __launch_bounds__(256) void gf_rank_large_reduce(LargeParams p) {
-    __shared__ uint32_t tab[kTabDwords];
+    __shared__ uint32_t tab[kMulTabDw];
     __shared__ uint2 qh[4][kQTile];
     const int k = p.k, m = p.m;
     const LargeLayout L = large_layout(k, m);
@@ -97,7 +94,7 @@ __global__ __launch_bounds__(256) void gf_rank_large_reduce(LargeParams p) {
         stream_block(ws, L.B, t0, b);
         if (b <= 0) return;  // an idle object: nothing new in this block
     }
-    const int rank = (!STREAM && t0 == 0) ? 0 : __builtin_amdgcn_readfirstlane(int(ws[0]));
+    const int rank = (!STREAM && t0 == 0) ? 0 : __builtin_amdgcn_readfirstlane(int(ws[kStRank]));
     if (rank >= k) return;  // ReceivedAllPieces for the whole block: the step only answers
     const int32_t *piv = reinterpret_cast<const int32_t *>(ws + L.piv);
     const uint32_t *R = ws + L.r;
@@ -216,25 +213,24 @@ __global__ __launch_bounds__(256) void gf_rank_large_step(LargeParams p) {
     const int tid = int(threadIdx.x), lane = tid & 63;
     int t0 = p.t0, b = p.b;
     if constexpr (STREAM) stream_block(ws, L.B, t0, b);
-    const int rank0 = (!STREAM && t0 == 0) ? 0 : __builtin_amdgcn_readfirstlane(int(ws[0]));
+    const int rank0 = (!STREAM && t0 == 0) ? 0 : __builtin_amdgcn_readfirstlane(int(ws[kStRank]));
     int32_t *St = reinterpret_cast<int32_t *>(ws + L.st);
     if constexpr (STREAM) {
-        if (b <= 0) {  // an idle object.  "Rank before" still moves up to the rank: the update takes c = rank - rank
-                       // before and would otherwise apply the previous block's Q and new rows a second time
-            if (tid == 0) ws[1] = uint32_t(rank0);
+        if (b <= 0) {  // an idle object: kStRankBefore still moves up to the rank (rank_state.hpp)
+            if (tid == 0) ws[kStRankBefore] = uint32_t(rank0);
             return;
         }
         if (rank0 >= k) {  // the block's slots are consumed all the same: the snapshot tells them from pending ones
             __syncthreads();  // every wave has read the state that thread 0 rewrites
             for (int tt = tid; tt < b; tt += 256) St[t0 + tt] = RLNC_ERR_RECEIVED_ALL_PIECES;
             if (tid == 0) {
-                ws[1] = uint32_t(rank0);
-                ws[2] = uint32_t(t0 + b);
+                ws[kStRankBefore] = uint32_t(rank0);
+                ws[kStDone] = uint32_t(t0 + b);
             }
             return;
         }
     } else if (rank0 >= k) {  // nothing to do: the update sees no new rows, the final launch answers ReceivedAllPieces
-        if (tid == 0) ws[1] = uint32_t(rank0);
+        if (tid == 0) ws[kStRankBefore] = uint32_t(rank0);
         return;
     }
     int32_t *piv = reinterpret_cast<int32_t *>(ws + L.piv);
@@ -242,7 +238,7 @@ __global__ __launch_bounds__(256) void gf_rank_large_step(LargeParams p) {
     const uint32_t *X = ws + L.x;
     uint32_t *R = ws + L.r;
     uint32_t *tab = lds;
-    uint32_t *Xs = lds + kTabDwords;  // the block's rows, then the small arrays
+    uint32_t *Xs = lds + kMulTabDw;  // the block's rows, then the small arrays
     const uint8_t *XsB = reinterpret_cast<const uint8_t *>(Xs);
     int32_t *npiv = reinterpret_cast<int32_t *>(Xs + size_t(L.B) * D);  // pivot column of new row s
     int32_t *nrow = npiv + kLargeMaxB;                                  // its row of Xs
@@ -395,20 +391,20 @@ __global__ __launch_bounds__(256) void gf_rank_large_step(LargeParams p) {
         }
     }
     if (tid == 0) {
-        ws[1] = uint32_t(rank0);
-        ws[0] = uint32_t(rank0 + c);
-        ws[2] = uint32_t(t0 + b);
+        ws[kStRankBefore] = uint32_t(rank0);
+        ws[kStRank] = uint32_t(rank0 + c);
+        ws[kStDone] = uint32_t(t0 + b);
     }
 }
 
 __global__ __launch_bounds__(256) void gf_rank_large_update(LargeParams p) {
-    __shared__ uint32_t tab[kTabDwords];
+    __shared__ uint32_t tab[kMulTabDw];
     const LargeLayout L = large_layout(p.k, p.m);
     const int D = L.D;
     const int chunk = int(blockIdx.x) % p.chunks, rest = int(blockIdx.x) / p.chunks;
     uint32_t *ws = p.ws + int64_t(rest / p.row_chunks) * p.ws_obj;
-    const int rank = __builtin_amdgcn_readfirstlane(int(ws[0]));
-    const int rprev = __builtin_amdgcn_readfirstlane(int(ws[1]));
+    const int rank = __builtin_amdgcn_readfirstlane(int(ws[kStRank]));
+    const int rprev = __builtin_amdgcn_readfirstlane(int(ws[kStRankBefore]));
     const int c = rank - rprev;
     const int row0 = (rest % p.row_chunks) * kUpdRows;
     if (c <= 0 || row0 >= rprev) return;  // no new rows in this block, or no older rows in this chunk
@@ -467,8 +463,8 @@ __global__ __launch_bounds__(256) void gf_rank_large_final(LargeParams p) {
     const int tid = int(threadIdx.x);
     if constexpr (STREAM)
         if (p.T == nullptr && fc != 0) return;  // only T is spread over the row chunks
-    const int rank = __builtin_amdgcn_readfirstlane(int(ws[0]));
-    const int done = __builtin_amdgcn_readfirstlane(int(ws[2]));
+    const int rank = __builtin_amdgcn_readfirstlane(int(ws[kStRank]));
+    const int done = __builtin_amdgcn_readfirstlane(int(ws[kStDone]));
     const int32_t *piv = reinterpret_cast<const int32_t *>(ws + L.piv);
     const int32_t *St = reinterpret_cast<const int32_t *>(ws + L.st);
     const uint32_t *R = ws + L.r;
@@ -516,24 +512,23 @@ __global__ __launch_bounds__(256) void gf_rank_large_final(LargeParams p) {
 }
 
 // ---- decode streams: the small launches around the blocks of a push --------------------------------------------------
-// one thread per object; the state words {rank, rank before, done, target} are each object's first four dwords
+// one thread per object
 
 __global__ __launch_bounds__(256) void gf_rank_stream_init(uint32_t *ws, int64_t ws_obj, int nobj) {
     const int o = int(blockIdx.x) * 256 + int(threadIdx.x);
     if (o < nobj) *reinterpret_cast<uint4 *>(ws + int64_t(o) * ws_obj) = make_uint4(0u, 0u, 0u, 0u);
 }
 
-// the latch: target = min(max(avail, done), m, done + max_new), kept in the state so that no later launch of the push
-// reads avail.  A done outside [0, m] (a state the library did not write) leaves the object idle.
+// the latch: the push target rule of rank_state.hpp, written out (the host passes max_new <= m)
 __global__ __launch_bounds__(256) void gf_rank_stream_latch(uint32_t *ws, int64_t ws_obj, int nobj,
                                                            const int32_t *avail, int m, int max_new) {
     const int o = int(blockIdx.x) * 256 + int(threadIdx.x);
     if (o >= nobj) return;
     uint32_t *st = ws + int64_t(o) * ws_obj;
-    const int done = int(st[2]);
+    const int done = int(st[kStDone]);
     int target = done;
     if (done >= 0 && done < m) target = min(min(max(avail[o], done), m), done + min(max_new, m - done));
-    st[3] = uint32_t(target);
+    st[kStTarget] = uint32_t(target);
 }
 
 __global__ __launch_bounds__(256) void gf_rank_stream_progress(const uint32_t *ws, int64_t ws_obj, int nobj,
@@ -541,8 +536,8 @@ __global__ __launch_bounds__(256) void gf_rank_stream_progress(const uint32_t *w
     const int o = int(blockIdx.x) * 256 + int(threadIdx.x);
     if (o >= nobj) return;
     const uint32_t *st = ws + int64_t(o) * ws_obj;
-    if (rank != nullptr) rank[o] = int32_t(st[0]);
-    if (answered != nullptr) answered[o] = int32_t(st[2]);
+    if (rank != nullptr) rank[o] = int32_t(st[kStRank]);
+    if (answered != nullptr) answered[o] = int32_t(st[kStDone]);
 }
 
 // the 160 KiB dynamic-LDS attribute of the block step (both forms), once per device
@@ -558,12 +553,9 @@ struct LargeGrids {
 };
 hipError_t large_setup(const RrefParams &rp, const void *ws, size_t ws_bytes, LargeParams &p, LargeGrids &g) {
     if (rp.objs != nullptr) return hipErrorInvalidValue;
-    const int B = large_block(rp.k, rp.m);
-    if (B == 0 || ws == nullptr || (reinterpret_cast<uintptr_t>(ws) & 15) != 0 ||
-        ws_bytes < rank_large_workspace_bytes(size_t(rp.k), size_t(rp.m), size_t(rp.n_obj)))
-        return hipErrorInvalidValue;
+    if (rank_state_check(rp.k, rp.m, rp.n_obj, ws, ws_bytes) != hipSuccess) return hipErrorInvalidValue;
     const LargeLayout L = large_layout(rp.k, rp.m);
-    g.step_lds = kLargeStepFixedBytes + size_t(B) * size_t(L.D) * 4;
+    g.step_lds = kLargeStepFixedBytes + size_t(L.B) * size_t(L.D) * 4;
     if (g.step_lds > kRrefMaxLds) return hipErrorInvalidValue;
     p = LargeParams{};
     p.pieces = rp.pieces;

@@ -1,18 +1,17 @@
 // rank_stream.hip — the LDS form of a decode stream's push (include/rlnc_hip.h, "Decode streams"; interface:
-// rank_stream_kernels.hpp; the state buffer and the workspace form: rank_large_kernels.hpp, rank_large.hip).
+// rank_stream_kernels.hpp; the state buffer, its words and their protocol: rank_state.hpp; the workspace form:
+// rank_large.hip).
 //
-// One launch per push.  Per object the kernel reads the state words once -- done, rank and avail, each through
-// readfirstlane -- and takes target = min(max(avail, done), m, done + max_new), b = target - done new slots:
-//   b <= 0     the object is idle: no word of its state is written (the workgroup form returns before any barrier, the
-//              wave form after the one table barrier);
-//   rank = k   the slots done .. target - 1 are answered ReceivedAllPieces and done moves up, as the workspace form's
-//              block step does;
+// One launch per push.  Per object the kernel reads done, rank and avail[o] once, each through readfirstlane, and takes
+// the target by rank_state.hpp's rule, b = target - done new slots:
+//   b <= 0     the object is idle (the workgroup form returns before any barrier, the wave form after the one table
+//              barrier);
+//   rank = k   the slots done .. target - 1 are answered ReceivedAllPieces and done moves up, as in the workspace step;
 //   otherwise  piv[0 .. rank) and R[0 .. rank)[D] come into LDS (the state's rows have rank.hip's layout, [c | e] of
 //              D dwords in arrival order), the headers of the b new slots are staged (bytes past k zero), and rank.hip's
 //              per-piece loop (reduce, pivot, insert) runs over them with unit(t) at the slot's own index t.  Rank k
 //              inside the push: ReceivedAllPieces for the rest of it.  Then St[done .. target) goes back, piv[0 .. rank')
-//              and R[0 .. rank')[D] too when a row was inserted (an insert rewrites the older rows), and last the state
-//              words {rank', rank', target, target}.
+//              and R[0 .. rank')[D] too when a row was inserted (an insert rewrites the older rows), last the words.
 // Q, X, the rows and pivots at or beyond rank' and the statuses at or beyond target are never touched.  rank / answered
 // (when given) are written for every object.  avail[o] is read exactly once, here, so no latch launch is needed: the
 // caller may rewrite avail once the call returned, and a captured push reads it anew at every replay.
@@ -20,11 +19,11 @@
 // The LDS region of an object is rank.hip's (rank_lds_bytes): it holds m staged headers and m statuses, of which a push
 // uses its b first.  TPO = threads per object, 256 (a workgroup per object) or 64 (a wave per object, four objects per
 // workgroup over one table copy), as in rank.hip.  Rules kept: every branch around a barrier is uniform over the
-// object's threads, on values read after the previous barrier and passed through readfirstlane (the state words are
-// read before the first barrier and written after the last); no workgroup waits for another; plain vector loads and
-// stores only.  The per-piece loop is a copy of rank.hip's.  Factored into one shared inline function it compiled the
-// one-shot kernels to the same instructions, but with commuted operands, two registers renamed and one address
-// computation moved; rank.hip stays as it is, so that its kernels keep their code to the byte.
+// object's threads, on values read after the previous barrier and passed through readfirstlane (the state words:
+// rank_state.hpp); no workgroup waits for another; plain vector loads and stores only.  The per-piece loop is a copy
+// of rank.hip's.  Factored into one shared inline function it compiled the one-shot kernels to the same instructions,
+// but with commuted operands, two registers renamed and one address computation moved; rank.hip stays as it is, so
+// that its kernels keep their code to the byte.
 #include "../../include/rlnc_hip.h"
 #include "gf_perm.hpp"
 #include "rref.hpp"
@@ -33,8 +32,6 @@
 namespace rlnc {
 
 namespace {
-
-constexpr int kRankTabDw = 256 * kTabDw;  // the multipliers 0..255 of kRrefTable (8 KiB)
 
 struct StreamLdsParams {
     const uint8_t *pieces;
@@ -65,11 +62,11 @@ __global__ __launch_bounds__(256) void gf_rank_stream_push(StreamLdsParams p) {
     int32_t *gSt = reinterpret_cast<int32_t *>(ws + p.off_st);
     uint32_t *R = ws + p.off_r;
 
-    // the state, once.  A done or rank the library did not write (outside [0, m) / below 0) leaves the object idle.
+    // the state, once; the push target rule of rank_state.hpp, written out (a rank below 0 leaves the object idle too)
     int done = 0, rank0 = 0, b = 0;
     if (valid) {
-        done = __builtin_amdgcn_readfirstlane(int(ws[2]));
-        rank0 = __builtin_amdgcn_readfirstlane(int(ws[0]));
+        done = __builtin_amdgcn_readfirstlane(int(ws[kStDone]));
+        rank0 = __builtin_amdgcn_readfirstlane(int(ws[kStRank]));
         const int av = __builtin_amdgcn_readfirstlane(p.avail[o]);
         if (done >= 0 && done < m && rank0 >= 0) b = min(min(max(av, done), m), done + p.max_new) - done;
     }
@@ -82,7 +79,7 @@ __global__ __launch_bounds__(256) void gf_rank_stream_push(StreamLdsParams p) {
     auto answer_full = [&]() {
         for (int t = tid; t < b; t += TPO) gSt[done + t] = RLNC_ERR_RECEIVED_ALL_PIECES;
         if (tid == 0) {
-            *reinterpret_cast<uint4 *>(ws) = make_uint4(uint32_t(rank0), uint32_t(rank0), uint32_t(target), uint32_t(target));
+            store_state(ws, rank0, target);
             progress(rank0);
         }
     };
@@ -98,7 +95,7 @@ __global__ __launch_bounds__(256) void gf_rank_stream_push(StreamLdsParams p) {
         }
     }
 
-    uint32_t *rows = lds + kRankTabDw + size_t(int(threadIdx.x) / TPO) * size_t(p.obj_dw);
+    uint32_t *rows = lds + kMulTabDw + size_t(int(threadIdx.x) / TPO) * size_t(p.obj_dw);
     uint8_t *rowsB = reinterpret_cast<uint8_t *>(rows);
     uint32_t *vb = rows + k * D;  // two scratch rows, alternating by piece
     uint32_t *Hw = vb + 2 * D;    // the staged headers of the new slots, kd dwords each (room for m)
@@ -248,7 +245,7 @@ __global__ __launch_bounds__(256) void gf_rank_stream_push(StreamLdsParams p) {
         for (int i = 4 * n4 + tid; i < nR; i += TPO) R[i] = rows[i];
     }
     if (tid == 0) {
-        *reinterpret_cast<uint4 *>(ws) = make_uint4(uint32_t(rank), uint32_t(rank), uint32_t(target), uint32_t(target));
+        store_state(ws, rank, target);
         progress(rank);
     }
 }
@@ -270,10 +267,9 @@ bool rank_stream_lds_fits(size_t k, size_t m) {
 hipError_t launch_rank_stream_push_lds(const RrefParams &rp, void *state, size_t state_bytes, const int32_t *avail,
                                        int max_new, int32_t *rank, int32_t *answered, hipStream_t s) {
     if (rp.n_obj <= 0 || max_new <= 0) return hipSuccess;
-    if (avail == nullptr || rp.pieces == nullptr || rp.objs != nullptr || rp.k <= 0 || rp.m <= 0) return hipErrorInvalidValue;
-    const size_t need = rank_stream_state_bytes(size_t(rp.k), size_t(rp.m), size_t(rp.n_obj));
-    if (!rank_stream_lds_fits(size_t(rp.k), size_t(rp.m)) || need == 0 || state == nullptr ||
-        (reinterpret_cast<uintptr_t>(state) & 15) != 0 || state_bytes < need)
+    if (avail == nullptr || rp.pieces == nullptr || rp.objs != nullptr) return hipErrorInvalidValue;
+    if (rank_state_check(rp.k, rp.m, rp.n_obj, state, state_bytes) != hipSuccess ||
+        !rank_stream_lds_fits(size_t(rp.k), size_t(rp.m)))
         return hipErrorInvalidValue;
     const LargeLayout L = large_layout(rp.k, rp.m);
     const size_t lds = rank_lds_bytes(rp.k, rp.m);
@@ -294,10 +290,10 @@ hipError_t launch_rank_stream_push_lds(const RrefParams &rp, void *state, size_t
     p.off_st = int(L.st);
     p.off_r = int(L.r);
     p.D = L.D;
-    p.obj_dw = int((lds - size_t(kRankTabDw) * 4) / 4);
+    p.obj_dw = int((lds - size_t(kMulTabDw) * 4) / 4);
     // many small objects: a workgroup per object leaves most of its lanes idle and the grid launch-bound
     if (rp.k <= 16 && L.D <= 16 && rp.n_obj >= 1024) {
-        const size_t lds4 = size_t(kRankTabDw) * 4 + 4 * size_t(p.obj_dw) * 4;  // < 20 KiB
+        const size_t lds4 = size_t(kMulTabDw) * 4 + 4 * size_t(p.obj_dw) * 4;  // < 20 KiB
         hipLaunchKernelGGL(gf_rank_stream_push<64>, dim3((unsigned(rp.n_obj) + 3) / 4), dim3(256), lds4, s, p);
         return hipGetLastError();
     }

@@ -1,13 +1,11 @@
 // rank_stream_kernels.hpp — launch interface of the LDS form of a decode stream's push (rank_stream.hip; internal to
 // librlnc_hip).
 //
-// A second producer of a decode stream's state (include/rlnc_hip.h, "Decode streams"; the state buffer, its layout and
-// the workspace form of the push: rank_large_kernels.hpp).  One launch per push: each object's stored rows and pivots
-// come from the state into LDS, rank.hip's per-piece loop runs over the object's new slots only, and the rows, pivots,
-// statuses and state words go back.  The state after a push is the one-piece-at-a-time model's after the same pieces,
-// as it is after a push of the workspace form, and the rows of that state are unique (rank_large.hip's proof), so the
-// two forms may be mixed from push to push on one state buffer: this form writes all four state words, and the
-// workspace form rewrites words 1 and 3 and its scratch (Q, X) before it reads them.
+// A second producer of a decode stream's state (include/rlnc_hip.h, "Decode streams"; the state buffer, its words and
+// why the two forms may be mixed from push to push on one buffer: rank_state.hpp; the workspace form of the push:
+// rank_large_kernels.hpp).  One launch per push: each object's stored rows and pivots come from the state into LDS,
+// rank.hip's per-piece loop runs over the object's new slots only, and the rows, pivots, statuses and state words go
+// back.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,7 +13,7 @@
 #include <cstdint>
 
 #include "rank_kernels.hpp"
-#include "rank_large_kernels.hpp"
+#include "rank_state.hpp"
 #include "rref.hpp"
 
 namespace rlnc {

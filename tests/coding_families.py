@@ -8,7 +8,7 @@ tests can assert that they reach it.  Plain module: no GPU, no library."""
 import numpy as np
 
 from tests.gpu_util import np_matmul
-from tests.test_true_rank_host import FIXTURE, FIXTURE_K, OK
+from tests.true_rank import FIXTURE, FIXTURE_K, OK
 
 NAMES = ["identity", "reversed", "shift", "perm", "upper", "upper_rev", "lower", "lower_rev", "band", "gf2", "halves",
          "highspan", "fixture_blocks", "lowrank", "dupzero"]

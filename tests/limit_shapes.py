@@ -13,7 +13,7 @@ MUL = npo.mul_table()
 MAX_LDS = 160 * 1024  # kRrefMaxLds (rref.hpp)
 
 
-# ---- rank_large.hip (rank_large_kernels.hpp) -------------------------------------------------------------------------
+# ---- rank_large.hip (rank_state.hpp) ---------------------------------------------------------------------------------
 LARGE_MAX_K, LARGE_MAX_M, LARGE_MAX_B = 4096, 8192, 32
 LARGE_STEP_FIXED = 8192 + 1024  # kLargeStepFixedBytes: the multiplier table, the small arrays
 
@@ -38,15 +38,20 @@ def _up4(v):
     return (v + 3) & ~3
 
 
-def large_layout_total(k, m):
-    """Dwords of one object's workspace: state[4], piv[k], St[m], Q[k][8], X[B][D], R[k][D], each array from a multiple
-    of 4."""
+def large_layout(k, m):
+    """rank_state.hpp's large_layout, one object's state in dwords: the four state words, piv[k], St[m], Q[k][8],
+    X[B][D], R[k][D], each array from a multiple of 4.  The offsets from the state words, D and the total."""
     D, B = large_row_dwords(k, m), large_block(k, m)
-    st = _up4(4 + k)
+    piv = 4
+    st = _up4(piv + k)
     q = _up4(st + m)
     x = q + k * (LARGE_MAX_B // 4)
     r = _up4(x + B * D)
-    return _up4(r + k * D)
+    return dict(piv=piv, st=st, q=q, x=x, r=r, total=_up4(r + k * D), D=D)
+
+
+def large_layout_total(k, m):
+    return large_layout(k, m)["total"]
 
 
 # ---- rank.hip --------------------------------------------------------------------------------------------------------
@@ -255,6 +260,41 @@ def planted3(rng, k, m):
     co[m // 3] = co[7] ^ co[m // 5]
     co[2 * m // 3] = MUL[0x1D][co[m // 2]]
     return co
+
+
+def combos(rng, basis, n):
+    """n random GF(2^8) combinations of the basis rows."""
+    return np_matmul(rng.integers(0, 256, (n, basis.shape[0]), dtype=np.uint8), basis)
+
+
+def block_cases(rng, k, m, B):
+    """Three objects of m pieces whose dependencies sit on the block boundaries (pieces B at a time):
+    a  block 0 spans only 8 dimensions (a zero piece, a duplicate inside the block); block 1 is useless as a whole
+       (c = 0: combinations, a multiple of an earlier block's piece, a zero piece); later blocks are dense;
+    b  dense with a zero piece and a duplicate: rank k is reached inside block 0, ReceivedAllPieces from there on;
+    c  block 0 spans 15 dimensions; block 1 starts with a multiple of an earlier block's piece, a new piece, the XOR
+       of that new piece and a stored one, a zero piece, then dense pieces: rank k is reached inside block 1."""
+    n = max(m, 3 * B)
+    a = np.zeros((n, k), np.uint8)
+    basis = rng.integers(0, 256, (8, k), dtype=np.uint8)
+    a[:B] = combos(rng, basis, B)
+    a[1] = 0
+    a[5] = a[2]
+    a[B:2 * B] = combos(rng, basis, B)
+    a[B] = MUL[0x1D][a[3]]
+    a[B + 2] = 0
+    a[2 * B:] = rng.integers(0, 256, (n - 2 * B, k), dtype=np.uint8)
+    b = rng.integers(0, 256, (n, k), dtype=np.uint8)
+    b[3] = 0
+    b[6] = b[4]
+    b[B] = MUL[7][b[1]]
+    c = np.zeros((n, k), np.uint8)
+    c[:B] = combos(rng, rng.integers(0, 256, (15, k), dtype=np.uint8), B)
+    c[B:] = rng.integers(0, 256, (n - B, k), dtype=np.uint8)
+    c[B] = MUL[0x53][c[2]]
+    c[B + 2] = c[3] ^ c[B + 1]
+    c[B + 3] = 0
+    return np.stack([a[:m], b[:m], c[:m]])
 
 
 def blocks_of(statuses, B):

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from tests import coding_families as cf
-from tests.test_true_rank_host import NOT_USEFUL, OK, RECEIVED_ALL, check_against_model
+from tests.true_rank import NOT_USEFUL, OK, RECEIVED_ALL, check_against_model
 
 SHAPES = [(6, 8), (8, 12), (16, 40), (24, 40), (64, 72), (126, 130), (130, 132)]
 _memo = {}

@@ -1,88 +1,18 @@
 """CPU: a decode stream's compaction without a GPU (include/rlnc_hip.h, rlnc_decode_stream_compact) -- the symbol in the
-header, the ctypes table and the library, the refusals that need no device, and the numpy model of the call with the
-inputs that tests/test_gpu_decode_stream_compact.py runs on the device.
+header, the ctypes table and the library, the refusals that need no device, and the numpy model of the call
+(tests/stream_util.py) with the inputs that tests/test_gpu_decode_stream_compact.py runs on the device.
 
-compact_model is built on true_rank_model (tests/test_true_rank_host.py): the kept slots u are the prefix's Ok slots.
+compact_model is built on true_rank_model (tests/true_rank.py): the kept slots u are the prefix's Ok slots.
 The equivalence the call rests on is checked here on the CPU for every input family the GPU tests use: the model of the
 kept vectors alone answers Ok for every one of them, has the prefix's rank, and its T is the prefix's T with the columns
 gathered by u.  The same file asserts what every tested batch must hold, so that no GPU test can pass vacuously."""
 import ctypes as C
-import functools
 
 import numpy as np
 import pytest
 
-from oracle import np_oracle as npo
-from tests import limit_shapes as ls
-from tests.test_true_rank_host import NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
-
-MUL = npo.mul_table()
-# (5, 7) odd kd, m no multiple of 4; (16, 20) the form the default picks is the LDS one; (24, 67) B = 32, m no multiple
-# of 4; (4, 1100) rows wider than 256 dwords; (300, 330) a scan and a list beyond one pass of 256 threads; (4, 8192) the
-# most slots a stream takes: 32 statuses per thread of the scan, an e part of 2,048 dwords, slot indices up to 8,190
-SHAPES = [(5, 7), (16, 20), (24, 67), (4, 1100), (300, 330), (4, 8192)]
-NAMES = ["mixed", "chain", "late", "idle", "empty", "full", "sparse", "planted", "dense"]
-
-
-def model_of(k, vectors):
-    """true_rank_model, and the empty prefix."""
-    if len(vectors) == 0:
-        return [], 0, np.zeros((k, 0), np.uint8), None
-    return true_rank_model(k, vectors)
-
-
-def compact_model(k, co_prefix):
-    """What rlnc_decode_stream_compact does with an object whose pushed slots hold the vectors co_prefix: (u, r, T, st)
-    -- the kept slots u_0 < ... < u_{r-1} (the prefix's Ok slots), r = rank, T [k][r] the prefix's T with its columns
-    gathered by u, and the prefix's statuses."""
-    st, rank, T, _ = model_of(k, co_prefix)
-    u = [t for t, s in enumerate(st) if s == OK]
-    assert len(u) == rank
-    return u, rank, np.ascontiguousarray(T[:, u]), st
-
-
-@functools.lru_cache(maxsize=None)
-def cases(k, m):
-    """The batch of a shape: (co uint8 [9][m][k], done [9]) -- each object's coding vectors and how many of its slots
-    are pushed before the compaction (a strict prefix: done < m), in the order of NAMES:
-      mixed    dense with a zero piece, a duplicate and a multiple among the first slots
-      chain    slot 0 zero and every later pushed slot useful: u_j = j + 1 throughout, the longest overwrite chain
-      late     the first m - k slots zero, the others dense
-      idle     independent vectors only: done == rank > 0
-      empty    done == 0
-      full     dense: rank k, then ReceivedAllPieces slots below done
-      sparse   sparse_vectors at density 2
-      planted  limit_shapes.planted: duplicates, multiples and sums of earlier pieces
-      dense    dense random, pushed up to m - 2"""
-    rng = np.random.default_rng(7000 * k + m)
-    dense = lambda: rng.integers(1, 256, (m, k), dtype=np.uint8)  # noqa: E731
-    mixed = dense()
-    mixed[1] = 0
-    mixed[3] = mixed[2]
-    mixed[4] = MUL[0x1D][mixed[0]]
-    chain = dense()
-    chain[0] = 0
-    late = dense()
-    late[: m - k] = 0
-    co = np.stack([mixed, chain, late, dense(), dense(), dense(), sparse_vectors(rng, k, m, 2), ls.planted(rng, k, m),
-                   dense()])
-    done = [m - 1, min(m - 1, k + 1), m - 1, max(1, k - 2), 0, m - 1, m - 1, m - 1, m - 2]
-    co.setflags(write=False)
-    return co, tuple(done)
-
-
-@functools.lru_cache(maxsize=None)
-def prefix_models(k, m):
-    """compact_model of every object of cases(k, m), computed once."""
-    co, done = cases(k, m)
-    return tuple(compact_model(k, co[o, :done[o]]) for o in range(co.shape[0]))
-
-
-@functools.lru_cache(maxsize=None)
-def kept_models(k, m):
-    """true_rank_model of every object's kept vectors alone, computed once."""
-    co, _ = cases(k, m)
-    return tuple(model_of(k, co[o][u]) for o, (u, _, _, _) in enumerate(prefix_models(k, m)))
+from tests.stream_util import NAMES, SHAPES, cases, kept_models, model_of, prefix_models
+from tests.true_rank import NOT_USEFUL, OK, RECEIVED_ALL
 
 
 def test_symbol_is_declared_bound_and_exported():

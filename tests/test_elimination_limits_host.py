@@ -9,7 +9,7 @@ import pytest
 
 from rlnc_amd import batch
 from tests import limit_shapes as ls
-from tests.test_true_rank_host import NOT_USEFUL, OK, RECEIVED_ALL, host_run, true_rank_model
+from tests.true_rank import NOT_USEFUL, OK, RECEIVED_ALL, host_run, true_rank_model
 
 WIDER_THAN_A_ROW = {(130, 482), (269, 271)}  # test_lds_edges
 LARGE_SHAPES = sorted({(k, m) for k, m, _, _ in ls.LARGE_NARROW} | set(ls.LARGE_OTHER))

@@ -17,9 +17,9 @@ from oracle.oracle import OracleDecoder
 from tests import coding_families as cf
 from tests import limit_shapes as ls
 from tests.gpu_util import dev, host, np_matmul
-from tests.test_gpu_decode_stream import Prefixes, advance, check_snapshot, i32
+from tests.stream_util import Prefixes, advance, check_snapshot, i32, true_rank_context
 from tests.test_gpu_true_rank import check_decoded, check_eliminate
-from tests.test_true_rank_host import RECEIVED_ALL, true_rank_model
+from tests.true_rank import RECEIVED_ALL, true_rank_model
 
 pytestmark = pytest.mark.gpu
 
@@ -44,11 +44,7 @@ def ctx():
 
 @pytest.fixture(scope="module")
 def ctx1():
-    import rlnc_amd
-
-    c = rlnc_amd.Context(0)
-    c.set_rank_mode(1)
-    return c
+    return true_rank_context()
 
 
 # ---- the cases: one object per (family, shape, L, seed), its references computed once and left unchanged ------------

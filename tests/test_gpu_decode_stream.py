@@ -1,6 +1,6 @@
 """GPU: decode streams (include/rlnc_hip.h, "Decode streams"; rlnc_amd.batch.DecodeStream) -- the true-rank decode of
 rank_large.hip kept on the device between calls and pushed forward per object -- against the numpy model of
-tests/test_true_rank_host.py run on each object's own prefix.  All comparisons are exact.
+tests/true_rank.py run on each object's own prefix.  All comparisons are exact.
 
 After every push a snapshot must be the model of the slots pushed so far: statuses (pending beyond them), rank, T (zero
 columns beyond them), and the rank / answered arrays of the push itself.  The shapes are the smallest at which the
@@ -17,75 +17,21 @@ from oracle import np_oracle as npo
 from tests import limit_shapes as ls
 from tests.footprint import Arena, assert_inputs_unchanged
 from tests.gpu_util import dev, host
-from tests.test_gpu_large_generation import block_cases
-from tests.test_true_rank_host import NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
+from tests.limit_shapes import block_cases
+from tests.stream_util import (PENDING, Prefixes, advance, check_snapshot, i32, pieces_of, raw,
+                               true_rank_context)
+from tests.true_rank import NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PENDING, NOT_ALL_YET, INVALID = -1, 10, 100
+NOT_ALL_YET, INVALID = 10, 100
 LARGE = 8
 M28 = ls._M32 + 4  # B = 28
 
 
 @pytest.fixture(scope="module")
 def ctx1():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import rlnc_amd
-
-    c = rlnc_amd.Context(0)
-    c.set_rank_mode(1)
-    return c
-
-
-def i32(n, fill=-7):
-    import torch
-
-    return torch.full(n if isinstance(n, tuple) else (n,), fill, dtype=torch.int32, device="cuda:0")
-
-
-def pieces_of(co, L=4, seed=0):
-    """co [nobj][m][k] -> device pieces [nobj][m][k + L] with random data bytes (the elimination reads none)."""
-    nobj, m, k = co.shape
-    p = np.random.default_rng(seed).integers(0, 256, (nobj, m, k + L), dtype=np.uint8)
-    p[:, :, :k] = co
-    return dev(p)
-
-
-class Prefixes:
-    """true_rank_model of object o's first n slots, computed once per (o, n)."""
-
-    def __init__(self, k, co):
-        self.k, self.co, self.memo = k, co, {}
-
-    def __call__(self, o, n):
-        if (o, n) not in self.memo:
-            self.memo[(o, n)] = (true_rank_model(self.k, self.co[o, :n]) if n else
-                                 ([], 0, np.zeros((self.k, 0), np.uint8), None))
-        return self.memo[(o, n)]
-
-
-def advance(done, avail, m, max_new):
-    return [min(max(a, d), m, d + (m if max_new is None else max_new)) for d, a in zip(done, avail)]
-
-
-def check_snapshot(stream, model, done, tag):
-    import torch
-
-    nobj, k, m = stream.num_objects, stream.k, stream.m
-    T = torch.full((nobj, k, m), 0xAA, dtype=torch.uint8, device="cuda:0")
-    ps, rk = i32((nobj, m)), i32(nobj)
-    stream.snapshot(T, ps, rk)
-    T, ps, rk = host(T), host(ps), host(rk)
-    for o in range(nobj):
-        st, rank, Tm, _ = model(o, done[o])
-        assert list(ps[o, :done[o]]) == st, (tag, o)
-        assert (ps[o, done[o]:] == PENDING).all(), (tag, o)
-        assert rk[o] == rank, (tag, o, rk[o], rank)
-        assert np.array_equal(T[o][:, :done[o]], Tm), (tag, o)
-        assert not T[o][:, done[o]:].any(), (tag, o)
-    return ps, rk
+    return true_rank_context()
 
 
 def run_schedule(ctx, k, co, rounds):
@@ -269,9 +215,6 @@ def test_end_to_end(ctx1):
 
 # ---- refusals: every one on the host, before a launch ------------------------------------------------------------------
 
-def raw(ctx, fn, *args):
-    return getattr(ctx.lib, fn)(ctx.h, *args)
-
 
 def test_refusals(ctx1):
     import torch
@@ -400,7 +343,7 @@ import numpy as np
 import torch
 import rlnc_amd
 from rlnc_amd import batch
-from tests.test_gpu_large_generation import block_cases
+from tests.limit_shapes import block_cases
 
 k, m, B, L = 24, 67, 32, 4
 co = block_cases(np.random.default_rng(31), k, m, B)

@@ -1,6 +1,6 @@
 """GPU: a decode stream's compaction (include/rlnc_hip.h, rlnc_decode_stream_compact; rlnc_amd/csrc/rank_compact.hip;
-rlnc_amd.batch.DecodeStream.compact) against the numpy model of tests/test_decode_stream_compact_host.py, which also
-asserts what the batches used here hold.  All comparisons are exact.
+rlnc_amd.batch.DecodeStream.compact) against the numpy model of tests/stream_util.py;
+tests/test_decode_stream_compact_host.py asserts what the batches used here hold.  All comparisons are exact.
 
 After a compaction the live state -- state words 0 and 2, piv[0..rank), St[0..done), R[0..rank)[D] -- must be, byte for
 byte, that of a second stream that was initialised and pushed the kept pieces alone; kept / answered must be the
@@ -18,12 +18,10 @@ import pytest
 from oracle import np_oracle as npo
 from tests.footprint import Arena
 from tests.gpu_util import dev, host
-from tests.test_decode_stream_compact_host import (NAMES, SHAPES, cases, compact_model, kept_models, model_of,
-                                                   prefix_models)
-from tests.test_gpu_decode_stream import check_snapshot, i32, pieces_of, raw
-from tests.test_gpu_decode_stream_lds import large_layout, live_state, state_words
-from tests.test_gpu_large_generation import block_cases
-from tests.test_true_rank_host import OK
+from tests.limit_shapes import block_cases, large_layout
+from tests.stream_util import (NAMES, SHAPES, cases, check_snapshot, compact_model, i32, kept_models, live_state,
+                               model_of, pieces_of, prefix_models, raw, state_words, true_rank_context)
+from tests.true_rank import OK
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -34,14 +32,7 @@ PIECE_CASES = [(5, 7, 21), (16, 20, 4099), (24, 67, 8209)]  # k, m, k + L
 
 @pytest.fixture(scope="module")
 def ctx1():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import rlnc_amd
-
-    c = rlnc_amd.Context(0)
-    c.set_rank_mode(1)
-    return c
+    return true_rank_context()
 
 
 def tens(v):
@@ -145,7 +136,7 @@ def arrivals(rng, k, n):
             junk[i] = junk[i - 2]
         elif i % 4 == 3:
             junk[i] = npo.mul_table()[0x53][junk[i - 3]]
-    from tests.test_true_rank_host import sparse_vectors
+    from tests.true_rank import sparse_vectors
 
     sparse = np.concatenate([sparse_vectors(rng, k, n - k, 2), rng.integers(1, 256, (k, k), dtype=np.uint8)])
     return np.stack([slow, dense, junk, sparse])
@@ -452,8 +443,8 @@ import torch
 import rlnc_amd
 from oracle import np_oracle as npo
 from rlnc_amd import batch
-from tests.test_gpu_large_generation import block_cases
-from tests.test_true_rank_host import true_rank_model
+from tests.limit_shapes import block_cases
+from tests.true_rank import true_rank_model
 
 k, m, L, n, per = 24, 28, 4, 96, 4
 co = block_cases(np.random.default_rng(34), k, n, 32)

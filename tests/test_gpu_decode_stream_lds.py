@@ -1,6 +1,6 @@
 """GPU: the LDS form of a decode stream's push (include/rlnc_hip.h, rlnc_set_stream_form; rlnc_amd/csrc/rank_stream.hip)
-against the numpy model of tests/test_true_rank_host.py run on each object's own prefix, with the helpers of
-tests/test_gpu_decode_stream.py.  All comparisons are exact.
+against the numpy model of tests/true_rank.py run on each object's own prefix, with the helpers of
+tests/stream_util.py.  All comparisons are exact.
 
 Under form 2 a snapshot after every push must be the model of the slots pushed so far (T, statuses with PENDING, rank),
 and so must the push's own rank / answered arrays.  The two forms alternated push by push must leave the live state --
@@ -22,8 +22,9 @@ from oracle import np_oracle as npo
 from tests import limit_shapes as ls
 from tests.footprint import Arena, assert_inputs_unchanged
 from tests.gpu_util import dev, host
-from tests.test_gpu_decode_stream import Prefixes, advance, check_snapshot, i32, pieces_of, raw
-from tests.test_true_rank_host import NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
+from tests.stream_util import (Prefixes, advance, check_snapshot, i32, live_state, pieces_of, raw, state_words,
+                               true_rank_context)
+from tests.true_rank import NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -35,45 +36,7 @@ BEYOND16 = [beyond for fit, beyond in ls.RANK_EDGES if fit[0] == 16][0]  # the f
 
 @pytest.fixture(scope="module")
 def ctx1():
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import rlnc_amd
-
-    c = rlnc_amd.Context(0)
-    c.set_rank_mode(1)
-    return c
-
-
-def large_layout(k, m):
-    """rank_large_kernels.hpp's large_layout: dword offsets of piv, St, Q, X, R from an object's four state words."""
-    D, B = ls.large_row_dwords(k, m), ls.large_block(k, m)
-    piv = 4
-    st = ls._up4(piv + k)
-    q = ls._up4(st + m)
-    x = q + k * (ls.LARGE_MAX_B // 4)
-    r = ls._up4(x + B * D)
-    total = ls._up4(r + k * D)
-    assert total == ls.large_layout_total(k, m)
-    return dict(piv=piv, st=st, q=q, x=x, r=r, total=total, D=D)
-
-
-def state_words(image, k, m, nobj):
-    """A state buffer's host image (uint8) as uint32 [nobj][total]."""
-    total = large_layout(k, m)["total"]
-    return np.ascontiguousarray(image[: nobj * total * 4]).view(np.uint32).reshape(nobj, total)
-
-
-def live_state(image, k, m, nobj):
-    """What a later call reads of each object: (rank, done, piv[0..rank), St[0..done), R[0..rank)[D])."""
-    lay = large_layout(k, m)
-    out = []
-    for w in state_words(image, k, m, nobj):
-        rank, done = int(w[0]), int(w[2])
-        assert 0 <= rank <= k and 0 <= done <= m
-        out.append((rank, done, w[lay["piv"]: lay["piv"] + rank].tobytes(), w[lay["st"]: lay["st"] + done].tobytes(),
-                    w[lay["r"]: lay["r"] + rank * lay["D"]].tobytes()))
-    return out
+    return true_rank_context()
 
 
 def inputs(rng, k, m):
@@ -316,7 +279,7 @@ def test_footprint(ctx1):
     from rlnc_amd import batch
 
     k, m, nobj, L = 24, 40, 4, 4
-    lay = large_layout(k, m)
+    lay = ls.large_layout(k, m)
     co = inputs(np.random.default_rng(77), k, m)
     co[3, 5] = co[3, 4]  # d's round-3 push inserts nothing
     model = Prefixes(k, co)
@@ -431,8 +394,8 @@ import numpy as np
 import torch
 import rlnc_amd
 from rlnc_amd import batch
-from tests.test_gpu_large_generation import block_cases
-from tests.test_true_rank_host import true_rank_model
+from tests.limit_shapes import block_cases
+from tests.true_rank import true_rank_model
 
 k, m, B, L = 24, 40, 8, 4
 co = block_cases(np.random.default_rng(32), k, 3 * B, B)

@@ -9,7 +9,7 @@
                   kernel's own LDS cap.
 
 A region undersized by a few dwords gives wrong bytes, not a fault, so every comparison is exact equality against a
-checker that is no device code: the numpy model of tests/test_true_rank_host.py in rank mode 1, OracleDecoder in rank
+checker that is no device code: the numpy model of tests/true_rank.py in rank mode 1, OracleDecoder in rank
 mode 0, tests.gpu_util.np_matmul for products.  Output buffers start as 0xAA or -1."""
 import contextlib
 import functools
@@ -22,7 +22,8 @@ from oracle.oracle import OracleDecoder
 from tests import limit_shapes as ls
 from tests.gpu_util import dev, host, np_matmul
 from tests.test_gpu_parity import S, _sequences
-from tests.test_true_rank_host import NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
+from tests.stream_util import true_rank_context
+from tests.true_rank import NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
 
 pytestmark = pytest.mark.gpu
 NOT_ALL_YET = 10
@@ -43,7 +44,7 @@ def _context(rank_mode):
 @pytest.fixture(scope="module")
 def ctx1():
     """A context in rank mode 1 (tests set its decode path through `path` and get path 0 back)."""
-    return _context(1)
+    return true_rank_context()
 
 
 @pytest.fixture(scope="module")

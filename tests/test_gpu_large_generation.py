@@ -1,7 +1,7 @@
 """GPU: the true-rank elimination for generations beyond LDS (rlnc_amd/csrc/rank_large.hip) -- decode path 8 (those
 kernels for every shape) at the smallest shapes at which they can go wrong, and decode path 7 (the device for every
 shape) through decode_batch_eliminate / decode_batch_device / decode_batch / decode_ragged / decode_host_stream --
-against the numpy model of tests/test_true_rank_host.py.  All comparisons are exact."""
+against the numpy model of tests/true_rank.py.  All comparisons are exact."""
 import contextlib
 import ctypes as C
 import functools
@@ -11,7 +11,9 @@ import pytest
 
 from oracle import np_oracle as npo
 from tests.gpu_util import dev, host, np_matmul
-from tests.test_true_rank_host import FIXTURE, NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
+from tests.limit_shapes import block_cases
+from tests.stream_util import true_rank_context
+from tests.true_rank import FIXTURE, NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors, true_rank_model
 
 pytestmark = pytest.mark.gpu
 NOT_ALL_YET = 10
@@ -20,7 +22,7 @@ MUL = npo.mul_table()
 
 
 def block_pieces(k, m):
-    """Pieces per block of rank_large.hip (rank_large_kernels.hpp, large_block): the largest multiple of 4, at most
+    """Pieces per block of rank_large.hip (rank_state.hpp, large_block): the largest multiple of 4, at most
     32, whose rows fit the block step's LDS beside 8 KiB + 1 KiB."""
     D = (k + 3) // 4 + (m + 3) // 4
     return min(32, (160 * 1024 - 8192 - 1024) // (4 * D)) & ~3
@@ -29,14 +31,7 @@ def block_pieces(k, m):
 @pytest.fixture(scope="module")
 def ctx1():
     """A context in rank mode 1 (tests set its decode path through `path` and get path 0 back)."""
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import rlnc_amd
-
-    c = rlnc_amd.Context(0)
-    c.set_rank_mode(1)
-    return c
+    return true_rank_context()
 
 
 @contextlib.contextmanager
@@ -79,11 +74,6 @@ def check_eliminate(ctx, co, L=4, pad_pieces=0, models=None):
     return models
 
 
-def combos(rng, basis, n):
-    """n random GF(2^8) combinations of the basis rows."""
-    return np_matmul(rng.integers(0, 256, (n, basis.shape[0]), dtype=np.uint8), basis)
-
-
 def planted(rng, k, m):
     """Dense vectors with planted duplicates, multiples and sums of earlier pieces."""
     co = rng.integers(0, 256, (m, k), dtype=np.uint8)
@@ -91,36 +81,6 @@ def planted(rng, k, m):
         a, b = rng.integers(0, i, 2)
         co[i] = [co[a], MUL[int(rng.integers(2, 256))][co[a]], co[a] ^ co[b]][i % 3]
     return co
-
-
-def block_cases(rng, k, m, B):
-    """Three objects of m pieces whose dependencies sit on the block boundaries (pieces B at a time):
-    a  block 0 spans only 8 dimensions (a zero piece, a duplicate inside the block); block 1 is useless as a whole
-       (c = 0: combinations, a multiple of an earlier block's piece, a zero piece); later blocks are dense;
-    b  dense with a zero piece and a duplicate: rank k is reached inside block 0, ReceivedAllPieces from there on;
-    c  block 0 spans 15 dimensions; block 1 starts with a multiple of an earlier block's piece, a new piece, the XOR
-       of that new piece and a stored one, a zero piece, then dense pieces: rank k is reached inside block 1."""
-    n = max(m, 3 * B)
-    a = np.zeros((n, k), np.uint8)
-    basis = rng.integers(0, 256, (8, k), dtype=np.uint8)
-    a[:B] = combos(rng, basis, B)
-    a[1] = 0
-    a[5] = a[2]
-    a[B:2 * B] = combos(rng, basis, B)
-    a[B] = MUL[0x1D][a[3]]
-    a[B + 2] = 0
-    a[2 * B:] = rng.integers(0, 256, (n - 2 * B, k), dtype=np.uint8)
-    b = rng.integers(0, 256, (n, k), dtype=np.uint8)
-    b[3] = 0
-    b[6] = b[4]
-    b[B] = MUL[7][b[1]]
-    c = np.zeros((n, k), np.uint8)
-    c[:B] = combos(rng, rng.integers(0, 256, (15, k), dtype=np.uint8), B)
-    c[B:] = rng.integers(0, 256, (n - B, k), dtype=np.uint8)
-    c[B] = MUL[0x53][c[2]]
-    c[B + 2] = c[3] ^ c[B + 1]
-    c[B + 3] = 0
-    return np.stack([a[:m], b[:m], c[:m]])
 
 
 # ---- path 8: the workspace-resident kernels at every shape -------------------------------------------------------------

@@ -267,7 +267,7 @@ def test_round_trip_with_a_true_rank_receiver():
     common.  The model reaches rank 33 at piece 46 with 13 PieceNotUseful before it."""
     import rlnc_amd
     from rlnc_amd import batch
-    from tests.test_true_rank_host import sparse_vectors, true_rank_model
+    from tests.true_rank import sparse_vectors, true_rank_model
 
     k, L, m = 33, 257, 132
     vectors = sparse_vectors(np.random.default_rng(0), k, m, 3)

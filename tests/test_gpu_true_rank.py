@@ -1,7 +1,7 @@
 """GPU: rank mode 1 (RLNC_RANK_MODE_TRUE; include/rlnc_hip.h, "Rank mode") through every public layer -- the device
 kernel (rank.hip) behind decode_batch_eliminate / decode_batch_device / decode_batch / decode_ragged /
 decode_host_stream, the host fallback beyond LDS, the object API and the C++ mirror -- against the numpy model of
-tests/test_true_rank_host.py.  All comparisons are exact."""
+tests/true_rank.py.  All comparisons are exact."""
 import ctypes as C
 import os
 import subprocess
@@ -11,7 +11,8 @@ import pytest
 
 from oracle import np_oracle as npo
 from tests.gpu_util import dev, host
-from tests.test_true_rank_host import (FIXTURE, FIXTURE_K, NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors,
+from tests.stream_util import true_rank_context
+from tests.true_rank import (FIXTURE, FIXTURE_K, NOT_USEFUL, OK, RECEIVED_ALL, sparse_vectors,
                                        true_rank_model)
 
 pytestmark = pytest.mark.gpu
@@ -22,16 +23,7 @@ NOT_ALL_YET = 10
 @pytest.fixture(scope="module")
 def ctx1():
     """A context in rank mode 1 (tests that change its mode or path put it back)."""
-    import torch
-
-    assert torch.cuda.is_available(), "GPU tests need the MI355X"
-    import rlnc_amd
-
-    c = rlnc_amd.Context(0)
-    assert c.rank_mode == 0
-    c.set_rank_mode(1)
-    assert c.rank_mode == 1
-    return c
+    return true_rank_context()
 
 
 def eliminate(ctx, pieces_t, k):
