@@ -217,6 +217,12 @@ int rlnc_gf256_sparse_matmul(rlnc_context *ctx, const rlnc_sparse_matmul_desc *d
  * register-indexed XORs, 9 column runs.
  * max_tile_rows caps the output rows per launch/workgroup (0 = automatic, else 1/2/4/8/16/32). */
 int rlnc_set_kernel_variant(rlnc_context *ctx, int variant, int max_tile_rows);
+/* Persistent tiles of the 64-row product (variant 8 above 32 output rows, batch calls on the context's stream): 0 =
+ * chosen per launch (from two tiles per compute unit on), 1 = never (the one-tile-per-workgroup grid), 2 = every launch
+ * the program takes, however few its tiles (tests).  max_workgroups: 0 = one workgroup per compute unit, else (8 or
+ * more) at most that many, so that a small product gives each workgroup several tiles (tests).  Bit-identical for every
+ * value. */
+int rlnc_set_persistent_tiles(rlnc_context *ctx, int mode, int max_workgroups);
 /* Column blocks per workgroup of variant 9 (A/B build only; 0 = automatic, else 1..64).  Bit-identical for every
  * value. */
 int rlnc_set_column_run(rlnc_context *ctx, int col_run);

@@ -92,6 +92,7 @@ _SIGS = {
     "rlnc_gf256_matmul": (C.c_int, [vp, C.POINTER(MatmulDesc)]),
     "rlnc_gf256_sparse_matmul": (C.c_int, [vp, C.POINTER(SparseMatmulDesc)]),
     "rlnc_set_kernel_variant": (C.c_int, [vp, C.c_int, C.c_int]),
+    "rlnc_set_persistent_tiles": (C.c_int, [vp, C.c_int, C.c_int]),
     "rlnc_set_column_run": (C.c_int, [vp, C.c_int]),
     "rlnc_set_decode_path": (C.c_int, [vp, C.c_int]),
     "rlnc_set_rank_mode": (C.c_int, [vp, C.c_int]),

@@ -84,6 +84,12 @@ class Context:
         reference's 4-bit tables, ablation).  The diagnostic A/B build adds 2-5 and 9.  All are bit-identical."""
         check(self.lib.rlnc_set_kernel_variant(self.h, int(variant), int(max_tile_rows)), self.lib)
 
+    def set_persistent_tiles(self, mode: int = 0, max_workgroups: int = 0):
+        """Persistent tiles of the 64-row product: 0 = chosen per launch, 1 = never, 2 = every launch the program takes
+        (tests); max_workgroups: 0 = one per compute unit, else at most that many (>= 8; tests).  Bit-identical for
+        every value."""
+        check(self.lib.rlnc_set_persistent_tiles(self.h, int(mode), int(max_workgroups)), self.lib)
+
     def set_column_run(self, col_run: int = 0):
         """Column blocks per workgroup of variant 9 (0 = automatic)."""
         check(self.lib.rlnc_set_column_run(self.h, int(col_run)), self.lib)

@@ -1,7 +1,7 @@
 // bsj_tile.hpp — the tile body of the bit-sliced jump programs (the generated inline-asm programs of
 // bitslice_jump.inc, gen_bsjump.py): one workgroup's output rows x one 4 KiB column block.  Shared by the uniform
-// kernels of kernels.hip, the ragged ones of ragged.hip and the column-run A/B variant of kernels_ab.hip (internal to
-// librlnc_hip).
+// kernels of kernels.hip (the persistent one among them), the ragged ones of ragged.hip and the column-run A/B variant
+// of kernels_ab.hip (internal to librlnc_hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,10 +9,14 @@
 
 #include "../../include/rlnc_hip.h"
 #include "bitslice_jump.inc"
+#include "bitslice_jump_persist.inc"
 #include "gf256.hpp"
 #include "kernels.hpp"
 #include "kernels_common.hpp"
 
+static_assert(RLNC_BSJ_P_SLOTS8 == RLNC_BSJ_SLOTS8 && RLNC_BSJ_P_CSET_BYTES8 == RLNC_BSJ_CSET_BYTES8 &&
+                  RLNC_BSJ_P_CS_SET8 == RLNC_BSJ_CS_SET8 && RLNC_BSJ_P_CS_BASE2_8 == RLNC_BSJ_CS_BASE2_8,
+              "bitslice_jump_persist.inc and bitslice_jump.inc come from different generator runs (LDS layout)");
 #ifndef RLNC_BSJ_SOFFSETS
 #error "bitslice_jump.inc must be generated with packed blocks (gen_bsjump.py default)"
 #endif
@@ -86,9 +90,20 @@ __device__ __forceinline__ void bsj_tile_scan(const MatmulParams &p, int obj) {
     }
 }
 
-template <int W, bool SHARE, bool RUN>
+// PERSIST (W = 8, RUN; one row tile): the persistent program (RLNC_BSJ_ASM_W8P).  The workgroup stays for the whole
+// launch: (obj, cb) is its first tile, index `first` of the tiles its counter hands out in order (tile = column block
+// fastest, then object), and every later tile is a claim: atomic add on *counter, index = claim_base + old value, the
+// workgroup ends with the first claim that is not below `limit`.
+struct BsjClaim {
+    uint32_t *counter = nullptr;
+    uint32_t claim_base = 0, limit = 0, first = 0;
+    uint32_t col_blocks = 1;
+};
+
+template <int W, bool SHARE, bool RUN, bool PERSIST = false>
 __device__ __forceinline__ void bsj_tile(const MatmulParams &p, const void *stream, int row_tiles, int rt, int cb,
-                                         int obj, uint32_t tiles, uint64_t *probe) {
+                                         int obj, uint32_t tiles, uint64_t *probe, const BsjClaim &claim = BsjClaim{}) {
+    static_assert(!PERSIST || (W == 8 && SHARE && RUN), "the persistent program is the 8-wave column-run program's");
     constexpr int kTileRows = kBsjWaveRows * W;
     // W = 8: one workgroup per CU, so a deeper ring and 2 BAR8 set slots (the builders run BAR8 rows ahead); the
     // 4-wave shared program may take the same form (gen_bsjump.py --w4bar: RLNC_BSJ_SLOTS4S ring slots); W = 1: a
@@ -100,7 +115,7 @@ __device__ __forceinline__ void bsj_tile(const MatmulParams &p, const void *stre
     __shared__ __attribute__((aligned(16))) uint8_t cset[SHARE ? (W == 8 ? RLNC_BSJ_CSET_BYTES8 : RLNC_BSJ_CSET_BYTES) : 16];
     const int row0 = rt * kTileRows;
     const int rows = min(kTileRows, p.n_out - row0);
-    if (p.hdr != nullptr && cb == 0) copy_header_rows(p, obj, row0, rows, 64 * W);
+    if (!PERSIST && p.hdr != nullptr && cb == 0) copy_header_rows(p, obj, row0, rows, 64 * W);  // PERSIST: the kernel
     const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const uint32_t lane = threadIdx.x & 63u;
     // the split 2-wave program (gen_bsjump.py --w2split): wave w owns the 2 KiB half w of the column block in all
@@ -153,7 +168,27 @@ __device__ __forceinline__ void bsj_tile(const MatmulParams &p, const void *stre
     if constexpr (W == 4 && !SHARE) asm volatile(RLNC_BSJ_ASM_W4 : RLNC_BSJ_OPERANDS);
     if constexpr (W == 4 && SHARE) asm volatile(RLNC_BSJ_ASM_W4S : RLNC_BSJ_OPERANDS);
     if constexpr (W == 8 && !RUN) asm volatile(RLNC_BSJ_ASM_W8S : RLNC_BSJ_OPERANDS);
-    if constexpr (W == 8 && RUN) asm volatile(RLNC_BSJ_ASM_W8R : RLNC_BSJ_OPERANDS);
+    if constexpr (W == 8 && RUN && !PERSIST) asm volatile(RLNC_BSJ_ASM_W8R : RLNC_BSJ_OPERANDS);
+    if constexpr (PERSIST) {
+        __shared__ uint32_t claimed;  // wave 0 publishes each claim here (one of the program's barriers orders it)
+        const uint32_t ldsp = uint32_t(reinterpret_cast<uintptr_t>((lds_u8 *)&claimed));
+        // past an object's last column block the next tile is the next object's first: what the pointers move by then
+        const int64_t in_wrap = p.in_obj - int64_t(claim.col_blocks) * kBsjColBlock;
+        const int64_t out_wrap = p.out_obj - int64_t(claim.col_blocks) * kBsjColBlock;
+        // (the program takes half = wave & 1 and cons = wave >> 2 from the wave index: scalar operands are scarce)
+        static_assert(kStageWaves == 4, "half and cons as the persistent program derives them");
+        asm volatile(RLNC_BSJ_ASM_W8P
+                     :
+                     : [src] "s"(src), [idx] "s"(idx), [dst] "s"(dst), [in_row] "s"(uint32_t(p.in_row)),
+                       [out_row] "s"(uint32_t(p.out_row)), [n_in] "s"(p.n_in), [rows] "s"(rows_w), [ldsw] "s"(ldsw),
+                       [off] "v"(off), [dmaoff] "v"(dmaoff), [ldsc] "v"(ldsc), [ldscw] "v"(ldscw),
+                       [ldsrg] "v"(ldsrg), [wave] "s"(uint32_t(w)), [ctr] "s"(claim.counter), [claim0] "s"(claim.claim_base),
+                       [limit] "s"(claim.limit), [curi] "s"(claim.first), [cb] "s"(uint32_t(cb)),
+                       [colb] "s"(claim.col_blocks), [inwrap_lo] "s"(uint32_t(uint64_t(in_wrap))),
+                       [inwrap_hi] "s"(uint32_t(uint64_t(in_wrap) >> 32)), [outwrap_lo] "s"(uint32_t(uint64_t(out_wrap))),
+                       [outwrap_hi] "s"(uint32_t(uint64_t(out_wrap) >> 32)), [ldsp] "v"(ldsp) RLNC_BSJ_P_BASE2_OPERANDS
+                     : RLNC_BSJ_CLOBBER_V, RLNC_BSJ_CLOBBER_S, RLNC_BSJ_CLOBBER_P);
+    }
 #undef RLNC_BSJ_OPERANDS
 #pragma clang diagnostic pop
     if constexpr (W <= 2 && !SHARE && !RUN)

@@ -238,8 +238,9 @@ struct rlnc_context {
     int device = 0;
     hipStream_t own = nullptr;
     hipStream_t stream = nullptr;
-    // variant 9 (column runs) is 5 % faster for an isolated encode launch but not in the bench's pipelined step,
-    // whose encode and decode launches share the CUs better with short workgroups (profiles/r02_run_ab.txt)
+    // variant 9 (static column runs, A/B build) is faster for an isolated encode launch but slower in the bench's
+    // pipelined step, where static runs unbalance the tail (profiles/r17_persistent_bound.txt); variant 8's persistent
+    // tiles (ws_claim below) remove the same prologue with run-time claims and are faster in both
     rlnc::MatmulVariant variant = rlnc::MatmulVariant::BitSlicedJumpShared8;
     int max_tile_rows = 0;
     int col_run = 0;  // column blocks per workgroup of variant 9 (0 = chosen per launch; rlnc_set_column_run)
@@ -285,6 +286,11 @@ struct rlnc_context {
     DevBuf ws_need;  // ... and its per-object "payload tail all zero" flags (RrefParams::tail_need)
     DevBuf ws_coef, ws_out, ws_status, ws_len, ws_pstat, ws_rank, ws_idx;
     DevBuf ws_large;  // the state of the workspace-resident true-rank elimination (rank_large.hip)
+    // the claim counters of the persistent 64-row product (kernels.hpp BsjPersist), zeroed once at creation.  One set
+    // per context is enough: only the batch calls on the context's stream use it, two of them are ordered by that
+    // stream, and each launch leaves the counters zero; contexts on other streams have their own.
+    DevBuf ws_claim;
+    int persist_mode = 0, persist_max_wgs = 0;  // rlnc_set_persistent_tiles
     PinBuf pin_a, pin_b, pin_c;
     // set once a batch call ran inside a HIP stream capture: the graph holds the workspace addresses, so
     // they must never move again (grow() refuses instead of reallocating)
@@ -563,7 +569,11 @@ struct rlnc_context {
         const size_t need = rlnc::matmul_scratch_bytes(p, v);
         if (need)
             if (int st = batch ? grow(idx, need) : idx.ensure(need)) return st;
-        HIP_TRY(rlnc::launch_matmul(p, s, v, idx.p, idx.cap));
+        rlnc::BsjPersist pt;
+        pt.counters = batch && s == stream ? ws_claim.as<uint32_t>() : nullptr;  // leased calls run on streams of their own
+        pt.mode = persist_mode;
+        pt.max_wgs = persist_max_wgs;
+        HIP_TRY(rlnc::launch_matmul(p, s, v, idx.p, idx.cap, pt));
         return RLNC_OK;
     }
 };

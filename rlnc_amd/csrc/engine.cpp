@@ -91,6 +91,13 @@ int rlnc_context_create(int device, rlnc_context **out) {
         return set_error(RLNC_ERR_DEVICE, "hipStreamCreate: %s", hipGetErrorString(e));
     }
     c->stream = c->own;
+    // the persistent product's claim counters: zero before the first launch, left zero by every launch (zeroed on the
+    // context's own stream: a legacy-stream memset would invalidate a capture in progress on another stream)
+    if (c->ws_claim.ensure(256) != RLNC_OK || hipMemsetAsync(c->ws_claim.p, 0, 256, c->own) != hipSuccess ||
+        hipStreamSynchronize(c->own) != hipSuccess) {
+        c->release();
+        return set_error(RLNC_ERR_OUT_OF_MEMORY, "context workspace");
+    }
     *out = c;
     return RLNC_OK;
 }
@@ -161,6 +168,15 @@ int rlnc_set_kernel_variant(rlnc_context *ctx, int variant, int max_tile_rows) {
               max_tile_rows == 8 || max_tile_rows == 16 || max_tile_rows == 32);
     ctx->variant = static_cast<rlnc::MatmulVariant>(variant);
     ctx->max_tile_rows = max_tile_rows;
+    return RLNC_OK;
+}
+
+int rlnc_set_persistent_tiles(rlnc_context *ctx, int mode, int max_workgroups) {
+    CHECK_ARG(ctx != nullptr);
+    CHECK_ARG(mode == rlnc::kBsjPersistAuto || mode == rlnc::kBsjPersistOff || mode == rlnc::kBsjPersistAlways);
+    CHECK_ARG(max_workgroups == 0 || (max_workgroups >= 8 && max_workgroups <= 65536));  // one per counter at least
+    ctx->persist_mode = mode;
+    ctx->persist_max_wgs = max_workgroups;
     return RLNC_OK;
 }
 

@@ -152,6 +152,21 @@ S_DTL, S_SRCT, S_DST0, S_TL, S_POS, S_NIN = 89, 90, 92, 94, 95, 96
 # vmcnt(1 + 32) for the two rows after a tile switch (so the next rows' DMA waits do not include the epilogue's
 # stores, which retire in issue order ahead of them): 1.4 % slower than a vmcnt(1) wait in every row.
 LAST_VGPR_ALL, LAST_SGPR_ALL = 243, 96
+# persistent program (RLNC_BSJ_ASM_W8P): the column-run program whose next tile comes from a claim on a counter in
+# device memory instead of "column block + 1" (one workgroup per CU for the whole launch).  Tile row 0: wave 0 adds 1
+# to the counter (one lane, vector atomic); row 1: it publishes base + old value through one LDS dword (the atomic is
+# older than the row's LDS-DMA, whose vmcnt wait at the row's top it therefore precedes); row 4: every wave reads the
+# dword -- one of the every-third-row barriers lies between -- and moves its next-tile pointers by the claim's distance
+# from the current tile (S_CB wraps into the next object).  The DMA stream enters the next tile at row n_in - DMA8, so
+# n_in >= PERSIST_MIN_SOURCES.  S_TL is 1 while a claimed tile follows (0: the tile is the workgroup's last), S_DTL 1
+# while the DMA stream has still to enter it.  S_TGT, S_TGT + 1 and S_T0 (free in the run programs) are temporaries.
+S_NDST, S_CB, S_CURI, S_EV = 98, 100, 101, 97  # next tile's dst (64-bit), column block, claim index, next event's S_CNT
+LAST_SGPR_P = 101
+V_CLAIM, V_PT = 244, 245  # the claim's result (lane 0, from row 0 to row 1); v245-v246: temporaries
+LAST_VGPR_P = 246
+PERSIST_ROWS = (0, 1, 4)  # tile rows of the claim, its publication and its use (1 + BAR8: set_bar8)
+PERSIST_MIN_SOURCES = 0   # set with DMA8 (set_bar8)
+STREAM_SHIFT8 = 9  # log2 of the 8-wave programs' STREAM_J_BYTES (64 rows x 8 bytes)
 
 DIAG = set()
 # The shared program raises the wave priority (s_setprio) for the calls from PRIO_AT[0] on and drops it after
@@ -458,11 +473,18 @@ def advance_run(L):
         f"s_addc_u32 s{S_SRC + 1}, s{S_SRC + 1}, 0",
         "s_branch 31f",
         "30:",
-        f"s_cmp_gt_u32 s{S_DTL}, 1",
-        "s_cbranch_scc0 31f",
-        f"s_sub_u32 s{S_DTL}, s{S_DTL}, 1",
-        f"s_add_u32 s{S_SRCT}, s{S_SRCT}, 4096",
-        f"s_addc_u32 s{S_SRCT + 1}, s{S_SRCT + 1}, 0",
+    ]
+    if PERSIST:  # the claimed tile's row 0 (S_SRCT, moved there by the claim's use), entered once
+        L += [f"s_cmp_eq_u32 s{S_DTL}, 1",
+              "s_cbranch_scc0 31f",
+              f"s_mov_b32 s{S_DTL}, 0"]
+    else:
+        L += [f"s_cmp_gt_u32 s{S_DTL}, 1",
+              "s_cbranch_scc0 31f",
+              f"s_sub_u32 s{S_DTL}, s{S_DTL}, 1",
+              f"s_add_u32 s{S_SRCT}, s{S_SRCT}, 4096",
+              f"s_addc_u32 s{S_SRCT + 1}, s{S_SRCT + 1}, 0"]
+    L += [
         f"s_mov_b64 s[{S_SRC}:{S_SRC + 1}], s[{S_SRCT}:{S_SRCT + 1}]",
         f"s_sub_u32 s{S_NDMA}, s{S_NIN}, 1",
         "31:",
@@ -470,6 +492,7 @@ def advance_run(L):
 
 
 RUN = False  # the 8-wave program being generated is the column-run form
+PERSIST = False  # ... its persistent form (RUN is set too)
 
 
 def own_set(L, rb, cslot):
@@ -699,28 +722,131 @@ def run_tail(L, unroll, body_fn):
     L.append("7:")
     # the run's last tile: the DMA stream's last (re-)reads must land before the workgroup ends (LDS); no other
     # vmcnt wait follows its stores
-    L += [f"s_cmp_eq_u32 s{S_TL}, 1", "s_cbranch_scc0 26f", "s_waitcnt vmcnt(0)", "26:"]
+    L += [f"s_cmp_eq_u32 s{S_TL}, {0 if PERSIST else 1}", "s_cbranch_scc0 26f", "s_waitcnt vmcnt(0)", "26:"]
     L.append(f"s_mov_b64 s[{S_DST}:{S_DST + 1}], s[{S_DST0}:{S_DST0 + 1}]")
     epilogue(L)  # the tile's rows (its own rows: S_ROWS), then fresh accumulators
     L += [f"v_mov_b32 v{r}, 0" for r in range(128)]
-    L += [f"s_sub_u32 s{S_TL}, s{S_TL}, 1",
-          f"s_cmp_eq_u32 s{S_TL}, 0",
-          "s_cbranch_scc1 3f",
-          f"s_add_u32 s{S_DST0}, s{S_DST0}, 4096",
-          f"s_addc_u32 s{S_DST0 + 1}, s{S_DST0 + 1}, 0",
-          f"s_mov_b32 s{S_CNT}, s{S_NIN}"]
+    if PERSIST:  # no claimed tile follows: the workgroup ends
+        L += [f"s_cmp_eq_u32 s{S_TL}, 0",
+              "s_cbranch_scc1 3f",
+              f"s_mov_b64 s[{S_DST0}:{S_DST0 + 1}], s[{S_NDST}:{S_NDST + 1}]",
+              f"s_mov_b32 s{S_CNT}, s{S_NIN}"]
+    else:
+        L += [f"s_sub_u32 s{S_TL}, s{S_TL}, 1",
+              f"s_cmp_eq_u32 s{S_TL}, 0",
+              "s_cbranch_scc1 3f",
+              f"s_add_u32 s{S_DST0}, s{S_DST0}, 4096",
+              f"s_addc_u32 s{S_DST0 + 1}, s{S_DST0 + 1}, 0",
+              f"s_mov_b32 s{S_CNT}, s{S_NIN}"]
     for j in range(unroll):  # continue with body j + 1
         nb = "1b" if j == unroll - 1 else f"{40 + j + 1}b"
         L += [f"s_cmp_eq_u32 s{S_POS}, {j}", f"s_cbranch_scc1 {nb}"]
     L += ["3:", "s_waitcnt lgkmcnt(0)"]
+    if PERSIST:
+        L.append("s_branch 34f")
+        persist_events(L, unroll)
+        L.append("34:")
+
+
+def persist_hook(L, j):
+    """Body j's top (after the barrier): the tile row is one with a claim event for this wave (S_EV) -> the handler
+    behind the loop, which comes back to label 80 + j."""
+    L += [f"s_cmp_eq_u32 s{S_CNT}, s{S_EV}",
+          "s_cbranch_scc0 32f",
+          f"s_mov_b32 s{S_POS}, {j}",
+          "s_branch 33f",
+          f"{80 + j}:",
+          "32:"]
+
+
+def persist_events(L, unroll):
+    """The claim events of the persistent program (see S_NDST): entered from persist_hook with S_CNT already counted
+    down for the row, so the tile row is S_NIN - 1 - S_CNT."""
+    r_claim, r_pub, r_use = PERSIST_ROWS
+    T, T1, T2 = S_TGT, S_TGT + 1, S_T0
+    L += ["33:",
+          f"s_sub_u32 s{T2}, s{S_NIN}, 1",
+          f"s_sub_u32 s{T2}, s{T2}, s{S_CNT}",
+          f"s_cmp_eq_u32 s{T2}, {r_claim}",
+          "s_cbranch_scc1 35f",
+          f"s_cmp_eq_u32 s{T2}, {r_pub}",
+          "s_cbranch_scc1 36f",
+          # row r_use, every wave: the claimed index; wave 0's next event is the next tile's claim
+          f"ds_read_b32 v{V_PT}, %[ldsp]",
+          "s_cmp_eq_u32 %[wave], 0",
+          f"s_cselect_b32 s{T2}, {r_use - r_claim}, 0",
+          f"s_add_u32 s{S_EV}, s{S_EV}, s{T2}",
+          f"s_mov_b32 s{S_TL}, 0",
+          "s_waitcnt lgkmcnt(0)",
+          f"v_readfirstlane_b32 s{T}, v{V_PT}",
+          "s_nop 4",
+          f"s_cmp_lt_u32 s{T}, %[limit]",
+          "s_cbranch_scc0 38f",  # at or past this counter's tiles: the current tile is the last
+          f"s_mov_b32 s{S_TL}, 1",
+          f"s_mov_b32 s{S_DTL}, 1",
+          f"s_sub_u32 s{T1}, s{T}, s{S_CURI}",  # tiles ahead (>= 1): the pointers move 4 KiB each
+          f"s_mov_b32 s{S_CURI}, s{T}",
+          f"s_add_u32 s{S_CB}, s{S_CB}, s{T1}",
+          f"s_lshl_b32 s{T}, s{T1}, 12",
+          f"s_lshr_b32 s{T2}, s{T1}, 20",
+          f"s_add_u32 s{S_NDST}, s{S_DST0}, s{T}",
+          f"s_addc_u32 s{S_NDST + 1}, s{S_DST0 + 1}, s{T2}",
+          f"s_add_u32 s{S_SRCT}, s{S_SRCT}, s{T}",
+          f"s_addc_u32 s{S_SRCT + 1}, s{S_SRCT + 1}, s{T2}",
+          "37:",  # past the object's last column block: on to the next object's first
+          f"s_cmp_ge_u32 s{S_CB}, %[colb]",
+          "s_cbranch_scc0 38f",
+          f"s_sub_u32 s{S_CB}, s{S_CB}, %[colb]",
+          f"s_add_u32 s{S_SRCT}, s{S_SRCT}, %[inwrap_lo]",
+          f"s_addc_u32 s{S_SRCT + 1}, s{S_SRCT + 1}, %[inwrap_hi]",
+          f"s_add_u32 s{S_NDST}, s{S_NDST}, %[outwrap_lo]",
+          f"s_addc_u32 s{S_NDST + 1}, s{S_NDST + 1}, %[outwrap_hi]",
+          f"s_lshl_b32 s{T}, s{S_NIN}, {STREAM_SHIFT8}",  # the object's rows in the block-address stream
+          f"s_add_u32 s{S_IDXM}, s{S_IDXM}, s{T}",
+          f"s_addc_u32 s{S_IDXM + 1}, s{S_IDXM + 1}, 0",
+          "s_branch 37b",
+          # row r_claim, wave 0: one lane adds 1 to the counter
+          "35:",
+          f"s_mov_b64 s[{T}:{T1}], exec",
+          "s_mov_b64 exec, 1",
+          "s_nop 1",
+          f"v_mov_b32 v{V_PT}, 0",
+          f"v_mov_b32 v{V_PT + 1}, 1",
+          f"global_atomic_add v{V_CLAIM}, v{V_PT}, v{V_PT + 1}, %[ctr] sc0",
+          f"s_mov_b64 exec, s[{T}:{T1}]",
+          f"s_sub_u32 s{S_EV}, s{S_EV}, {r_pub - r_claim}",
+          "s_branch 38f",
+          # row r_pub, wave 0: the claimed index into the LDS dword
+          "36:",
+          f"s_mov_b64 s[{T}:{T1}], exec",
+          "s_mov_b64 exec, 1",
+          "s_nop 1",
+          f"v_add_u32 v{V_CLAIM}, %[claim0], v{V_CLAIM}",
+          f"ds_write_b32 %[ldsp], v{V_CLAIM}",
+          f"s_mov_b64 exec, s[{T}:{T1}]",
+          "s_waitcnt lgkmcnt(0)",
+          f"s_sub_u32 s{S_EV}, s{S_EV}, {r_use - r_pub}",
+          "38:"]
+    for j in range(unroll):
+        L += [f"s_cmp_eq_u32 s{S_POS}, {j}", f"s_cbranch_scc1 {80 + j}b"]
 
 
 def run_init(L):
     L += [f"s_mov_b64 s[{S_SRCT}:{S_SRCT + 1}], %[src]",
-          f"s_mov_b64 s[{S_DST0}:{S_DST0 + 1}], %[dst]",
-          f"s_mov_b32 s{S_TL}, %[tiles]",
-          f"s_mov_b32 s{S_DTL}, %[tiles]",
-          f"s_mov_b32 s{S_NIN}, %[n_in]"]
+          f"s_mov_b64 s[{S_DST0}:{S_DST0 + 1}], %[dst]"]
+    if PERSIST:  # no next tile yet; wave 0's first event is the claim in row 0, the other waves' the use
+        assert STREAM_J_BYTES == 1 << STREAM_SHIFT8
+        L += [f"s_mov_b32 s{S_TL}, 0",
+              f"s_mov_b32 s{S_DTL}, 0",
+              f"s_mov_b32 s{S_CB}, %[cb]",
+              f"s_mov_b32 s{S_CURI}, %[curi]",
+              "s_cmp_eq_u32 %[wave], 0",
+              f"s_cselect_b32 s{S_EV}, {1 + PERSIST_ROWS[0]}, {1 + PERSIST_ROWS[2]}",
+              f"s_sub_u32 s{S_EV}, %[n_in], s{S_EV}"]
+    else:
+        L += [f"s_mov_b32 s{S_TL}, %[tiles]",
+              f"s_mov_b32 s{S_DTL}, %[tiles]"]
+    L.append(f"s_mov_b32 s{S_NIN}, %[n_in]")
 
 
 # 8-wave program: one workgroup per CU leaves LDS for SLOTS8 ring slots and CSLOTS8 = 2 BAR8 set slots, so the
@@ -741,6 +867,11 @@ PRIO8 = (4, 1)
 def set_bar8(b):
     global BAR8, DMA8, SLOTS8, CSLOTS8
     BAR8, DMA8, SLOTS8, CSLOTS8 = b, 2 * b + 2, {2: 6, 3: 12, 4: 16}[b], 2 * b
+    # the claim is used in tile row PERSIST_ROWS[2], before that row's DMA advance: the DMA stream enters the next
+    # tile in row n_in - DMA8 at the earliest; a barrier row lies in PERSIST_ROWS[1] + 1 .. PERSIST_ROWS[2]
+    global PERSIST_MIN_SOURCES, PERSIST_ROWS
+    PERSIST_ROWS = (0, 1, 1 + b)
+    PERSIST_MIN_SOURCES = DMA8 + PERSIST_ROWS[2]
 
 
 set_bar8(3)
@@ -782,6 +913,8 @@ def body_s8(L, j):
     L.append(f"s_sub_u32 s{S_CNT}, s{S_CNT}, 1")
     if PRIO8 is not None:
         L.append("s_setprio 0")
+    if PERSIST:
+        persist_hook(L, j)
     sfx, base = cslot_addr(j % CSLOTS8)
     # per-term diagnostics of the 8-wave unit (timing only, wrong results; scripts/archive/r06_unit_breakdown.sh):
     # s8noread no set reads, s8nodma no LDS-DMA of source rows, s8nostage no staging reads, s8noown the set writes
@@ -896,9 +1029,9 @@ def program_shared8():
         f"s_mov_b32 s{S_OUTROW}, %[out_row]",
         f"s_mov_b32 s{S_CNT}, %[n_in]",
         f"s_sub_u32 s{S_NDMA}, %[n_in], 1",
-        f"s_mov_b32 s{S_H}, %[half]",
+        f"s_mov_b32 s{S_H}, %[half]" if not PERSIST else f"s_and_b32 s{S_H}, %[wave], 1",
         f"s_mov_b32 s{S_ROWS}, %[rows]",
-        f"s_mov_b32 s{S_CONS}, %[cons]",
+        f"s_mov_b32 s{S_CONS}, %[cons]" if not PERSIST else f"s_lshr_b32 s{S_CONS}, %[wave], 2",
     ]
     if RUN:  # the wave's block-address stream start minus one row
         L += [f"s_sub_u32 s{S_IDXM}, s{S_IDX}, {STREAM_J_BYTES}", f"s_subb_u32 s{S_IDXM + 1}, s{S_IDX + 1}, 0"]
@@ -1329,6 +1462,10 @@ def main():
         body_txt = "\\n\\t".join(hinted(program_shared(cons=True)))
         RUN = False
         f.write(f'#define RLNC_BSJ_ASM_W8R "{body_txt}"\n')
+        global PERSIST
+        RUN = PERSIST = True
+        persist_txt = "\\n\\t".join(hinted(program_shared(cons=True)))
+        RUN = PERSIST = False
         f.write(f"#define RLNC_BSJ_SLOTS8 {SLOTS8}\n")
         if SOFFS is not None:  # block offsets of the shared programs' packed table (bsj_offset_kernel<true>)
             f.write("#define RLNC_BSJ_SOFFSETS {" + ", ".join(str(x) for x in SOFFS) + "}\n")
@@ -1337,6 +1474,25 @@ def main():
         f.write(f"#define RLNC_BSJ_CS_BASE2_8 {cs_base2()}\n")
         f.write(f"#define RLNC_BSJ_CLOBBER_V {clob_v}\n")
         f.write(f'#define RLNC_BSJ_CLOBBER_S {clob_s}, "m0", "scc", "memory"\n')
+    # the persistent program in a file of its own beside --out (bitslice_jump_persist.inc)
+    clob_p = ", ".join(f'"s{r}"' for r in range(LAST_SGPR_ALL + 1, LAST_SGPR_P + 1))
+    clob_p += ", " + ", ".join(f'"v{r}"' for r in range(LAST_VGPR_ALL + 1, LAST_VGPR_P + 1))
+    with open(os.path.splitext(args.out)[0] + "_persist.inc", "w") as f:
+        f.write("// GENERATED by gen_bsjump.py -- do not edit.  The persistent form of the 8-wave column-run program\n"
+                "// (gf_matmul_bsj_persist_kernel, kernels.hip); included after bitslice_jump.inc.\n")
+        f.write(f'#define RLNC_BSJ_ASM_W8P "{persist_txt}"\n')
+        f.write(f"#define RLNC_BSJ_PERSIST_MIN_SOURCES {PERSIST_MIN_SOURCES}\n")
+        f.write(f"#define RLNC_BSJ_CLOBBER_P {clob_p}\n")
+        # the second set-slot base, passed only where the program names it (an unused input still costs a VGPR)
+        base2 = "%[ldsc2]" in persist_txt or "%[ldscw2]" in persist_txt
+        f.write("#define RLNC_BSJ_P_BASE2_OPERANDS" +
+                (' , [ldsc2] "v"(ldsc + kCsBase2), [ldscw2] "v"(ldscw + kCsBase2)' if base2 else "") + "\n")
+        # the LDS layout this program was generated for: bsj_tile.hpp compares it with bitslice_jump.inc's, so a
+        # diagnostic build that substitutes only one of the two files does not compile
+        f.write(f"#define RLNC_BSJ_P_SLOTS8 {SLOTS8}\n")
+        f.write(f"#define RLNC_BSJ_P_CSET_BYTES8 {CSLOTS8 * CS_SLOT}\n")
+        f.write(f"#define RLNC_BSJ_P_CS_SET8 {CS_SET}\n")
+        f.write(f"#define RLNC_BSJ_P_CS_BASE2_8 {cs_base2()}\n")
 
 
 if __name__ == "__main__":

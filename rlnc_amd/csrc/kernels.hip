@@ -143,6 +143,51 @@ __global__ __launch_bounds__(64 * W) void gf_matmul_bsj_kernel(MatmulParams p, c
     bsj_tile<W, SHARE, false>(p, stream, row_tiles, rt, cb, obj, 1u, nullptr);
 }
 
+// Persistent tiles (the 8-wave program over one row tile, RLNC_BSJ_ASM_W8P): min(tiles, CUs) workgroups, one per CU,
+// stay for the whole launch.  Workgroup b serves counter x = b & 7 (the XCD it is dispatched to, as in decode_block):
+// counter x owns a contiguous eighth of the tiles (column block fastest, then object: an XCD's L2 sees a source column
+// block once and successive claims are neighbours), its workgroups start on its first tiles and claim the rest in
+// order, one tile ahead of their work.  counters[0..7] are the claims, counters[8] counts finished workgroups: the last
+// one to finish -- every claim of the launch is then made -- zeroes all nine, so the next launch needs no memset.
+// (A launch that does not run to its end -- a device fault or abort -- leaves them as they were; the context is lost
+// with the device then, like every other buffer of it, and nothing re-zeroes them.)
+__global__ __launch_bounds__(512) void gf_matmul_bsj_persist_kernel(MatmulParams p, const void *stream, int col_blocks,
+                                                                   uint32_t *counters) {
+    const uint32_t total = uint32_t(p.n_obj) * uint32_t(col_blocks), wgs = gridDim.x;
+    const uint32_t x = blockIdx.x & 7u, i = blockIdx.x >> 3;
+    const uint32_t q = total >> 3, r = total & 7u;
+    BsjClaim c;
+    c.counter = counters + x;
+    c.limit = q + (x < r ? 1u : 0u);                           // tiles of counter x
+    c.claim_base = (wgs >> 3) + (x < (wgs & 7u) ? 1u : 0u);    // ... of which its workgroups start on these
+    c.first = i;
+    c.col_blocks = uint32_t(col_blocks);
+    const uint32_t t = x * q + min(x, r) + i;
+    const int cb = int(t % uint32_t(col_blocks)), obj = int(t / uint32_t(col_blocks));
+    if (p.hdr != nullptr)
+        for (int o = blockIdx.x; o < p.n_obj; o += int(wgs)) copy_header_rows(p, o, 0, p.n_out, 512);
+    bsj_tile<8, true, true, true>(p, stream, 1, 0, cb, obj, 0u, nullptr, c);
+    if (threadIdx.x == 0) {  // wave 0 made the claims, the last of them long returned
+        const uint32_t done = __hip_atomic_fetch_add(counters + 8, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (done == wgs - 1)
+            for (int k = 0; k < kBsjPersistCounters; ++k)
+                __hip_atomic_store(counters + k, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+// compute units of the current device (looked up once per device)
+static int device_cus() {
+    static std::mutex mu;
+    static int cus[64] = {};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
+    std::lock_guard<std::mutex> lock(mu);
+    if (cus[dev] == 0 &&
+        (hipDeviceGetAttribute(&cus[dev], hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus[dev] <= 0))
+        cus[dev] = 256;
+    return cus[dev];
+}
+
 // the shared program's probe launch: stores its block table's address and returns (bsj_shared_base)
 __global__ __launch_bounds__(256) void gf_matmul_bsj_probe_kernel(MatmulParams p, const void *stream, uint64_t *probe) {
     bsj_tile<4, true, false>(p, stream, 1, 0, 0, 0, 1u, probe);
@@ -240,7 +285,7 @@ hipError_t bsj_prepare(const MatmulParams &p, hipStream_t s, void *scratch, size
 }
 
 static hipError_t launch_bsj(const MatmulParams &p, hipStream_t s, void *scratch, size_t scratch_bytes, int64_t &full,
-                      bool share, bool wide) {
+                      bool share, bool wide, const BsjPersist &pt) {
     BsjPlan b;
     hipError_t e = bsj_prepare(p, s, scratch, scratch_bytes, share, wide, b);
     full = b.full;
@@ -254,6 +299,17 @@ static hipError_t launch_bsj(const MatmulParams &p, hipStream_t s, void *scratch
                       p.out_row == p.width && p.out_obj == int64_t(p.scan_k) * p.width;
     if (!scan) q.scan_status = nullptr;
     const dim3 grid(unsigned(b.total));
+    // persistent tiles: the 64-row program over one row tile whose DMA stream stays within one tile of the work, from 2
+    // tiles per workgroup on (fewer: nothing to claim, the present grid is as good)
+    if (b.waves == 8 && b.share && pt.counters != nullptr && pt.mode != kBsjPersistOff && b.row_tiles == 1 &&
+        p.n_in >= RLNC_BSJ_PERSIST_MIN_SOURCES && p.n_in < (1 << 22)) {
+        const int64_t wgs = std::min<int64_t>(b.total, pt.max_wgs >= 8 ? pt.max_wgs : device_cus());
+        if (pt.mode == kBsjPersistAlways || b.total >= 2 * wgs) {
+            hipLaunchKernelGGL(gf_matmul_bsj_persist_kernel, dim3(unsigned(wgs)), dim3(512), 0, s, q, b.stream,
+                               b.col_blocks, pt.counters);
+            return hipGetLastError();
+        }
+    }
     if (b.waves == 1)
         hipLaunchKernelGGL(gf_matmul_bsj_kernel<1>, grid, dim3(64), 0, s, q, b.stream, b.row_tiles, b.col_blocks);
     else if (b.waves == 2)
@@ -523,7 +579,8 @@ size_t matmul_scratch_bytes_aligned(const MatmulParams &p, MatmulVariant v) {
     return bsj_eligible(p, matmul_aligned(p)) ? bsj_scratch_bytes(p, wide_variant(v)) : 0;
 }
 
-hipError_t launch_matmul(const MatmulParams &p, hipStream_t s, MatmulVariant v, void *scratch, size_t scratch_bytes) {
+hipError_t launch_matmul(const MatmulParams &p, hipStream_t s, MatmulVariant v, void *scratch, size_t scratch_bytes,
+                         const BsjPersist &pt) {
     if (p.n_out <= 0 || p.width <= 0 || p.n_obj <= 0) return hipSuccess;
     const bool aligned = matmul_aligned(p);
     if (p.n_in <= 0) return hipErrorInvalidValue;
@@ -564,7 +621,7 @@ hipError_t launch_matmul(const MatmulParams &p, hipStream_t s, MatmulVariant v, 
                     q.out_row = r.lr;
                     q.out_obj = int64_t(p.n_out) * r.lr;
                 }
-                if ((e = launch_matmul(q, s, v, scratch, r.prod_bytes)) != hipSuccess) return e;
+                if ((e = launch_matmul(q, s, v, scratch, r.prod_bytes, pt)) != hipSuccess) return e;
                 if (r.out_mis &&
                     (e = launch_realign(p.out + int64_t(o0) * p.out_obj + c0, p.out_row, p.out_obj, ob, r.lr,
                                         int64_t(p.n_out) * r.lr, p.n_out, w, c, s)) != hipSuccess)
@@ -587,7 +644,7 @@ hipError_t launch_matmul(const MatmulParams &p, hipStream_t s, MatmulVariant v, 
     if (jump) {
         if (bsj_eligible(p, aligned)) {
             int64_t full = 0;
-            hipError_t e = launch_bsj(p, s, scratch, scratch_bytes, full, share_variant(v), wide_variant(v));
+            hipError_t e = launch_bsj(p, s, scratch, scratch_bytes, full, share_variant(v), wide_variant(v), pt);
             if (e != hipSuccess || full == p.width) return e;
             return launch_matmul(tail_params(p, full), s, MatmulVariant::Perm);
         }

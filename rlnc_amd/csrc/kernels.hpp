@@ -73,8 +73,18 @@ size_t matmul_scratch_bytes(const MatmulParams &p, MatmulVariant v);
 int probe_unaligned_vector_access(int device);
 int unaligned_vector_access(int device);
 bool unaligned_vector_ok();
+// Persistent tiles of the 64-row product (kernels.hip gf_matmul_bsj_persist_kernel): kBsjPersistCounters zeroed dwords
+// of device memory that no other launch in flight uses (each launch leaves them zero), or nullptr: the present grid
+constexpr int kBsjPersistCounters = 9;
+enum : int { kBsjPersistAuto = 0, kBsjPersistOff = 1, kBsjPersistAlways = 2 };  // rlnc_set_persistent_tiles
+struct BsjPersist {
+    uint32_t *counters = nullptr;
+    int mode = kBsjPersistAuto;  // Always: every launch the program takes, however few its tiles (tests)
+    int max_wgs = 0;             // > 0 (>= 8, one per counter): at most that many workgroups instead of one per CU, so
+                                 // that small shapes give every workgroup several claimed tiles (tests)
+};
 hipError_t launch_matmul(const MatmulParams &p, hipStream_t stream, MatmulVariant v = MatmulVariant::Perm,
-                         void *scratch = nullptr, size_t scratch_bytes = 0);
+                         void *scratch = nullptr, size_t scratch_bytes = 0, const BsjPersist &persist = BsjPersist{});
 
 // ---- the A/B build (make ab: kernels_ab.hip adds matmul variants 2-5 and 9) ----
 // The shipped library defines these weakly (ab_build() false, the launches hipErrorInvalidValue); the A/B build's

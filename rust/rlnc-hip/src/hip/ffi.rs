@@ -192,6 +192,7 @@ unsafe extern "C" {
     pub fn rlnc_gf256_matmul(ctx: *mut rlnc_context, desc: *const rlnc_matmul_desc) -> c_int;
     pub fn rlnc_gf256_sparse_matmul(ctx: *mut rlnc_context, desc: *const rlnc_sparse_matmul_desc) -> c_int;
     pub fn rlnc_set_kernel_variant(ctx: *mut rlnc_context, variant: c_int, max_tile_rows: c_int) -> c_int;
+    pub fn rlnc_set_persistent_tiles(ctx: *mut rlnc_context, mode: c_int, max_workgroups: c_int) -> c_int;
     pub fn rlnc_set_column_run(ctx: *mut rlnc_context, col_run: c_int) -> c_int;
     pub fn rlnc_set_decode_path(ctx: *mut rlnc_context, path: c_int) -> c_int;
     pub fn rlnc_set_rank_mode(ctx: *mut rlnc_context, mode: c_int) -> c_int;

@@ -14,6 +14,12 @@ flags=""
 while [ $# -gt 0 ]; do
   if [ "$1" = "--" ]; then shift; flags="$*"; break; fi
   cp "${1#*=}" "$out/src/csrc/${1%%=*}"
+  # gen_bsjump.py writes the persistent program beside its --out file: a substituted bitslice_jump.inc takes it along
+  # (bsj_tile.hpp refuses a pair generated with different layouts)
+  if [ "${1%%=*}" = bitslice_jump.inc ]; then
+    sib="${1#*=}"; sib="${sib%.inc}_persist.inc"
+    [ -f "$sib" ] && cp "$sib" "$out/src/csrc/bitslice_jump_persist.inc"
+  fi
   shift
 done
 cxx="-O3 -std=c++17 -fPIC -Wall -Wextra -Wno-unused-parameter $flags"
