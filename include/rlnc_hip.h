@@ -69,7 +69,9 @@
  *     rlnc_decode_stream_compact (rlnc_amd/csrc/rank_compact.hip) reclaims the slots of useless arrivals and retires
  *     finished objects in place, on the device: the useful pieces move to the first slots, the columns of the stored
  *     rows are renumbered to match, and the state is a fresh stream's after the kept pieces -- so m bounds the pieces
- *     an object holds, not the arrivals it sees, and a place is reused while its neighbours go on.  Not covered: the
+ *     an object holds, not the arrivals it sees, and a place is reused while its neighbours go on.
+ *     rlnc_decode_stream_deliver (rlnc_amd/csrc/stream_deliver.hip) hands over the decoded data of the objects whose
+ *     rank is k, chosen on the device, at the cost of those objects' products alone.  Not covered: the
  *     reference rank mode has no stream form (a context in mode 0 is refused).  Measured on one MI355X
  *     (profiles/r12_decode_stream.jsonl, profiles/r14_stream_lds.jsonl, profiles/r16_stream_compact.jsonl): see
  *     DESIGN.md §4.2.4.
@@ -528,6 +530,46 @@ int rlnc_decode_stream_compact(rlnc_context *ctx, void *state_dev, size_t state_
  * (NotAllPiecesReceivedYet for an object below rank k). */
 int rlnc_decode_stream_snapshot(rlnc_context *ctx, const void *state_dev, size_t state_bytes, size_t k, size_t m,
                                 size_t num_objects, uint8_t *T_dev, int32_t *piece_status_dev, int32_t *rank_dev);
+/* Bytes of rlnc_decode_stream_deliver's plan buffer: the T extract [obj][k][m] and the block-address stream of the
+ * product (8 bytes per entry of ceil(k / tile rows) * tile rows x m coefficients per object, tile rows = 8, 16, 32 or 64
+ * by k).  A multiple of 16, at least num_objects * k * m; 0 exactly where rlnc_decode_stream_state_bytes is 0.  Pure:
+ * needs no context and no GPU. */
+size_t rlnc_decode_stream_deliver_plan_bytes(size_t k, size_t m, size_t num_objects);
+/* Delivers the finished objects of a stream, and only those, chosen on the device: the receive loop's middle call,
+ * push -> deliver -> compact(retire).  rank and done_o are taken as the last push or compaction left them (the
+ * context's stream orders the calls).  Per object o:
+ *   unselected   (select_dev != NULL and select_dev[o] == 0) nothing of the object is written: no byte of
+ *                decoded_dev[o], neither object_status_dev[o] nor data_len_dev[o].
+ *   rank < k     object_status_dev[o] = NotAllPiecesReceivedYet, data_len_dev[o] = 0; no byte of decoded_dev[o] is
+ *                written and no product work is done for it (its workgroups return on reading the state).
+ *   rank == k    decoded_dev[o] ([obj][k][L], all k * L bytes) = T_o x the data rows of slots 0 .. done_o - 1;
+ *                object_status_dev[o] and data_len_dev[o] exactly what rlnc_decode_batch_apply writes for the object: Ok
+ *                with the marker index, or InvalidDecodedDataFormat with 0.
+ * The state, the pieces and select_dev are only read: a later push continues from the state unchanged.  plan_dev is
+ * caller-owned scratch, 16-byte aligned and at least rlnc_decode_stream_deliver_plan_bytes long; its contents after the
+ * call are unspecified.
+ * Columns.  A delivering object's product takes done_o source rows, read on the device, not m (T's columns from done_o
+ * on are zero).  After rlnc_decode_stream_compact done_o = rank = k: the minimal k x k x L product.  Without a
+ * compaction it costs done_o / k of that, so a receiver with many useless arrivals calls compact, then deliver.
+ * Launches: at most five on the context's stream -- the snapshot's T extract, the block-address streams of the
+ * delivering objects, the bit-sliced product over the whole 4 KiB column blocks of L (the program of the batch
+ * products, one workgroup per object x row tile x column block), a perm-multiply product over what that does not take
+ * (L mod 4096; everything for k < 4 or operands the program refuses), the marker scan of the selected objects.  The
+ * call never synchronises and grows no context workspace, so (push, deliver, compact) can be captured as a linear HIP
+ * graph -- after one eager deliver on the device: the 32- and 64-row programs look up their block table once per
+ * device, synchronously, and a first deliver inside a capture runs every column in the perm-multiply kernel instead
+ * (the same bytes, slower).
+ * Checks in the order of push and compact: a null handle RLNC_ERR_INVALID_ARGUMENT; k == 0 PieceCountZero; L == 0
+ * PieceLengthZero; num_objects == 0 RLNC_OK, nothing launched; then the state and shape checks of push (rank mode 0, a
+ * buffer never initialised or initialised for another shape); pieces_obj_stride (0 = m*(k+L)) >= m*(k+L); pieces_dev,
+ * decoded_dev, object_status_dev and data_len_dev non-null; plan_dev non-null, aligned and long enough; every launch
+ * within 2^31 - 1 workgroups.  Each failure is RLNC_ERR_INVALID_ARGUMENT, names the limit in rlnc_last_error and
+ * writes nothing.  rlnc_decode_stream_snapshot + rlnc_decode_batch_apply remain the way to the product over every
+ * object; measurements of both: DESIGN.md §4.2.4, "Delivery". */
+int rlnc_decode_stream_deliver(rlnc_context *ctx, const void *state_dev, size_t state_bytes, const uint8_t *pieces_dev,
+                               size_t pieces_obj_stride, size_t k, size_t L, size_t m, size_t num_objects,
+                               const int32_t *select_dev, uint8_t *decoded_dev, int32_t *object_status_dev,
+                               int64_t *data_len_dev, void *plan_dev, size_t plan_bytes);
 
 /* ---- wire formats on the device ------------------------------------------------------------
  * Encoder::new's padded image (encoder.rs:85-106, BOUNDARY_MARKER consts.rs:5) built by a kernel from a byte

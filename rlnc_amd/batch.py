@@ -448,6 +448,14 @@ def stream_lds_fits(k: int, m: int) -> bool:
     return bool(load().rlnc_decode_stream_lds_fits(k, m))
 
 
+def stream_deliver_plan_bytes(k: int, m: int, num_objects: int) -> int:
+    """Device bytes of DecodeStream.deliver's plan buffer (rlnc_decode_stream_deliver_plan_bytes): a multiple of 16, 0
+    exactly where state_bytes is 0.  Needs no GPU."""
+    from ._lib import load
+
+    return int(load().rlnc_decode_stream_deliver_plan_bytes(k, m, num_objects))
+
+
 class DecodeStream:
     """The true-rank decoder state of num_objects objects (generation size k, m piece slots each) kept on the device
     between calls.  Slot t of object o is pieces[o][t] of the caller's pieces [obj][m][k+L] tensor; the caller fills
@@ -472,6 +480,7 @@ class DecodeStream:
         assert self.state.data_ptr() % 16 == 0
         self._T = None
         self._rank = None
+        self._plan = None
         c = _ctx_for(self.state, self.ctx)
         check(c.lib.rlnc_decode_stream_init(c.h, C.c_void_p(self.state.data_ptr()), nbytes, self.k, self.m,
                                             self.num_objects), c.lib)
@@ -550,3 +559,33 @@ class DecodeStream:
             self._rank = torch.empty((self.num_objects,), dtype=torch.int32, device=self.state.device)
         self.snapshot(T=self._T, rank=self._rank)
         decode_batch_apply(pieces, self.k, self._T, self._rank, decoded, object_status, data_len, self.ctx)
+
+    def deliver(self, pieces, decoded, object_status, data_len, select=None) -> None:
+        """The finished objects only, chosen on the device (rlnc_decode_stream_deliver): object o with rank k gets
+        decoded[o] ([obj][k][L]) = T_o x the data rows of its answered slots, object_status[o] Ok or
+        InvalidDecodedDataFormat and data_len[o]; an object below rank k gets NotAllPiecesReceivedYet and length 0, no
+        byte of decoded[o] and no product work; an object with select[o] == 0 (int32 [obj], optional) gets nothing
+        written at all.  The state and the pieces are only read.  The product takes done_o source rows: after
+        compact() that is k, the minimum -- a receiver with many useless arrivals compacts first.  The stream owns
+        the plan buffer and allocates it on the first call: call deliver once before capturing (push, deliver,
+        compact) into a graph -- that call also looks up the 32- and 64-row programs' block table, which a capture
+        cannot."""
+        import torch
+
+        L, obj_stride = self._pieces(pieces)
+        _chk(decoded, (self.num_objects, self.k, L))
+        n = (self.num_objects,)
+        os_ = self._i32(object_status, n, "object_status")
+        assert data_len.is_cuda and data_len.dtype == torch.int64 and data_len.is_contiguous() and \
+            tuple(data_len.shape) == n, "data_len: int64 contiguous device tensor of shape [obj] required"
+        sel = self._i32(select, n, "select") if select is not None else None
+        if self._plan is None:
+            nbytes = stream_deliver_plan_bytes(self.k, self.m, self.num_objects)
+            self._plan = torch.empty(nbytes, dtype=torch.uint8, device=self.state.device)
+            assert self._plan.data_ptr() % 16 == 0
+        c = _ctx_for(self.state, self.ctx)
+        check(c.lib.rlnc_decode_stream_deliver(c.h, C.c_void_p(self.state.data_ptr()), self.state.numel(),
+                                               C.c_void_p(pieces.data_ptr()), obj_stride, self.k, L, self.m,
+                                               self.num_objects, sel, C.c_void_p(decoded.data_ptr()), os_,
+                                               C.c_void_p(data_len.data_ptr()), C.c_void_p(self._plan.data_ptr()),
+                                               self._plan.numel()), c.lib)

@@ -1,8 +1,9 @@
 // decode_stream.cpp — the resumable device decode of librlnc_hip (include/rlnc_hip.h, "Decode streams"): the
 // true-rank decoder state of many objects in a caller-owned device buffer, pushed forward as pieces arrive
 // (rank_large.hip in its stream form, rank_large_kernels.hpp; for generations that fit LDS also the one-launch form of
-// rank_stream.hip, rank_stream_kernels.hpp), compacted in place (rank_compact.hip, rank_compact_kernels.hpp), and the
-// registry of initialised state buffers.  The state buffer itself: rank_state.hpp.
+// rank_stream.hip, rank_stream_kernels.hpp), compacted in place (rank_compact.hip, rank_compact_kernels.hpp), its
+// finished objects delivered (stream_deliver.hip, stream_deliver_kernels.hpp), and the registry of initialised state
+// buffers.  The state buffer itself: rank_state.hpp.
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -10,6 +11,7 @@
 #include "context.hpp"
 #include "rank_compact_kernels.hpp"
 #include "rank_stream_kernels.hpp"
+#include "stream_deliver_kernels.hpp"
 
 using namespace rlnc::eng;
 
@@ -176,6 +178,49 @@ int rlnc_decode_stream_snapshot(rlnc_context *ctx, const void *state, size_t sta
     rp.status = piece_status_dev;
     rp.rank = rank_dev;
     HIP_TRY(rlnc::launch_rank_stream_snapshot(rp, state, state_bytes, ctx->stream));
+    return RLNC_OK;
+}
+
+size_t rlnc_decode_stream_deliver_plan_bytes(size_t k, size_t m, size_t nobj) {
+    return rlnc::stream_deliver_plan_bytes(k, m, nobj);
+}
+
+int rlnc_decode_stream_deliver(rlnc_context *ctx, const void *state, size_t state_bytes, const uint8_t *pieces,
+                               size_t obj_stride, size_t k, size_t L, size_t m, size_t nobj, const int32_t *select,
+                               uint8_t *decoded, int32_t *object_status_dev, int64_t *data_len_dev, void *plan,
+                               size_t plan_bytes) {
+    CHECK_ARG(ctx != nullptr);
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    if (L == 0) return RLNC_ERR_PIECE_LENGTH_ZERO;
+    if (nobj == 0) return RLNC_OK;
+    int st = stream_args(ctx, state, state_bytes, k, m, nobj);
+    if (st || (st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
+    CHECK_ARG(L <= (size_t(1) << 40));  // m * (k + L) stays far inside 64 bits
+    if (obj_stride == 0) obj_stride = m * (k + L);
+    CHECK_ARG(obj_stride >= m * (k + L));
+    CHECK_ARG(pieces != nullptr && decoded != nullptr && object_status_dev != nullptr && data_len_dev != nullptr);
+    const size_t need = rlnc::stream_deliver_plan_bytes(k, m, nobj);
+    if (plan == nullptr || (reinterpret_cast<uintptr_t>(plan) & 15) != 0 || plan_bytes < need)
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "the delivery's plan buffer must be non-null, 16-byte aligned and at least "
+                         "rlnc_decode_stream_deliver_plan_bytes(k=%zu, m=%zu, %zu objects) = %zu bytes long (%p, %zu bytes)",
+                         k, m, nobj, need, plan, plan_bytes);
+    rlnc::DeliverParams p{};
+    p.pieces = pieces;
+    p.obj_stride = int64_t(obj_stride);
+    p.k = int(k), p.m = int(m), p.n_obj = int(nobj);
+    p.L = int64_t(L);
+    p.select = select;
+    p.decoded = decoded;
+    p.status = object_status_dev;
+    p.len = data_len_dev;
+    p.plan = plan;
+    if (!rlnc::stream_deliver_fits(p))
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "a delivery of %zu objects of k=%zu, m=%zu, L=%zu needs more than 2^31 - 1 workgroups in one "
+                         "launch: deliver fewer objects per call", nobj, k, m, L);
+    if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
+    HIP_TRY(rlnc::launch_stream_deliver(p, state, state_bytes, rlnc::unaligned_vector_ok(), ctx->stream));
     return RLNC_OK;
 }
 

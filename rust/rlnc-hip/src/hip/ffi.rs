@@ -540,6 +540,24 @@ unsafe extern "C" {
         piece_status_dev: *mut i32,
         rank_dev: *mut i32,
     ) -> c_int;
+    pub fn rlnc_decode_stream_deliver_plan_bytes(k: usize, m: usize, num_objects: usize) -> usize;
+    pub fn rlnc_decode_stream_deliver(
+        ctx: *mut rlnc_context,
+        state_dev: *const c_void,
+        state_bytes: usize,
+        pieces_dev: *const u8,
+        pieces_obj_stride: usize,
+        k: usize,
+        L: usize,
+        m: usize,
+        num_objects: usize,
+        select_dev: *const i32,
+        decoded_dev: *mut u8,
+        object_status_dev: *mut i32,
+        data_len_dev: *mut i64,
+        plan_dev: *mut c_void,
+        plan_bytes: usize,
+    ) -> c_int;
 
     // wire formats on the device
     pub fn rlnc_padded_piece_byte_len(data_len: usize, k: usize) -> usize;
