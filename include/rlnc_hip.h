@@ -169,7 +169,19 @@ int rlnc_gf256_mul_vec_by_scalar_then_add_into_vec(rlnc_context *ctx, uint8_t *d
  * Replaces the loop of gf256_mul_vec_by_scalar_then_add_into_vec calls in
  * Encoder::code_with_coding_vector (encoder.rs:138-141), batched over n_out coding vectors and n_obj
  * independent objects.  All strides in bytes.  hdr (optional, may be NULL) also receives the coefficient
- * rows, hdr[o][i][0:n_in) — the coeffs‖data framing of a full coded piece (encoder.rs:246-248). */
+ * rows, hdr[o][i][0:n_in) — the coeffs‖data framing of a full coded piece (encoder.rs:246-248).
+ * Strides (this descriptor and rlnc_sparse_matmul_desc), checked before any launch, else RLNC_ERR_INVALID_ARGUMENT:
+ *   - no stride is negative.  Any magnitude is addressed with 64 bits: objects or rows may lie more than 4 GiB apart
+ *     (the bit-sliced programs take row strides below 2^32; a product with a larger one runs on the perm kernels).
+ *   - what the call writes must not overlap, or its workgroups would race: with n_out > 1 the row stride of out is at
+ *     least width, with n_obj > 1 its object stride is at least width, and with both the objects lie outside each
+ *     other's rows, (n_out - 1) · row + width <= obj, or the rows outside each other's objects, (n_obj - 1) · obj +
+ *     width <= row.  The same for hdr (when not NULL) with n_in bytes in place of width.  The stride of a dimension of
+ *     one element is not used and may be anything >= 0.  out and hdr overlapping each other is not checked.
+ *   - what the call reads (in, coef; idx, val) may have stride 0: one source row, one source object, one coefficient
+ *     row or one coefficient matrix for all.
+ * n_obj is limited by the launch alone (n_obj · row tiles · column blocks below 2^31): 65,536 objects and more are one
+ * call. */
 typedef struct rlnc_matmul_desc {
     const uint8_t *in;
     int64_t in_obj_stride, in_row_stride;
@@ -586,7 +598,10 @@ typedef struct rlnc_pad_desc {
 size_t rlnc_padded_piece_byte_len(size_t data_len, size_t k); /* encoder.rs:93-95 (0 when k == 0) */
 int rlnc_pad_device(rlnc_context *ctx, const uint8_t *data_dev, size_t data_len, size_t k, uint8_t *out_dev,
                     size_t out_row_stride);
-int rlnc_pad_batch_device(rlnc_context *ctx, const rlnc_pad_desc *descs, size_t count); /* one launch */
+/* One launch for count descriptors; count <= 65,535 (RLNC_PAD_BATCH_MAX), else RLNC_ERR_INVALID_ARGUMENT and nothing
+ * is written: a caller with more splits its batch. */
+#define RLNC_PAD_BATCH_MAX 65535
+int rlnc_pad_batch_device(rlnc_context *ctx, const rlnc_pad_desc *descs, size_t count);
 /* Encoder::new from a device byte string: the encoder owns its padded image (built on the device). */
 int rlnc_encoder_new_device(rlnc_context *ctx, const uint8_t *data_dev, size_t data_len, size_t piece_count,
                             rlnc_encoder **out);

@@ -231,11 +231,28 @@ int rlnc_gf256_mul_vec_by_scalar_then_add_into_vec(rlnc_context *ctx, uint8_t *d
     return RLNC_OK;
 }
 
+// The raw descriptors' stride contract (rlnc_hip.h): an operand the call writes has strides >= 0 and rows that do not
+// overlap -- [n_obj][n_rows] rows of `bytes` bytes, objects outside each other's rows or rows outside each other's
+// objects (either nesting) -- and an operand it reads has strides >= 0 (0: one row or one object for all).
+static bool written_strides_ok(int64_t obj, int64_t row, int64_t n_obj, int64_t n_rows, int64_t bytes) {
+    if (obj < 0 || row < 0) return false;
+    const bool rows = n_rows > 1, objs = n_obj > 1;
+    if ((rows && row < bytes) || (objs && obj < bytes)) return false;
+    if (!rows || !objs) return true;
+    using i128 = __int128;
+    return i128(n_rows - 1) * row + bytes <= i128(obj) || i128(n_obj - 1) * obj + bytes <= i128(row);
+}
+
 int rlnc_gf256_matmul(rlnc_context *ctx, const rlnc_matmul_desc *desc) {
     CHECK_ARG(ctx != nullptr && desc != nullptr);
     CHECK_ARG(desc->n_out >= 0 && desc->n_in >= 0 && desc->width >= 0 && desc->n_obj >= 0);
     if (desc->n_out == 0 || desc->width == 0 || desc->n_obj == 0) return RLNC_OK;
     CHECK_ARG(desc->n_in > 0 && desc->in && desc->coef && desc->out);
+    CHECK_ARG(desc->in_obj_stride >= 0 && desc->in_row_stride >= 0 && desc->coef_obj_stride >= 0 &&
+              desc->coef_row_stride >= 0);
+    CHECK_ARG(written_strides_ok(desc->out_obj_stride, desc->out_row_stride, desc->n_obj, desc->n_out, desc->width));
+    CHECK_ARG(desc->hdr == nullptr ||
+              written_strides_ok(desc->hdr_obj_stride, desc->hdr_row_stride, desc->n_obj, desc->n_out, desc->n_in));
     int st = ctx->activate();
     if (st || (st = ctx->note_capture())) return st;
     rlnc::MatmulParams p{};
@@ -265,6 +282,11 @@ int rlnc_gf256_sparse_matmul(rlnc_context *ctx, const rlnc_sparse_matmul_desc *d
     CHECK_ARG(desc->n_in > 0 && desc->in && desc->out && (desc->w == 0 || (desc->idx && desc->val)));
     CHECK_ARG((reinterpret_cast<uintptr_t>(desc->idx) & 3) == 0 && (desc->idx_obj_stride & 3) == 0 &&
               (desc->idx_row_stride & 3) == 0);
+    CHECK_ARG(desc->in_obj_stride >= 0 && desc->in_row_stride >= 0 && desc->idx_obj_stride >= 0 &&
+              desc->idx_row_stride >= 0 && desc->val_obj_stride >= 0 && desc->val_row_stride >= 0);
+    CHECK_ARG(written_strides_ok(desc->out_obj_stride, desc->out_row_stride, desc->n_obj, desc->n_out, desc->width));
+    CHECK_ARG(desc->hdr == nullptr ||
+              written_strides_ok(desc->hdr_obj_stride, desc->hdr_row_stride, desc->n_obj, desc->n_out, desc->n_in));
     int st = ctx->activate();
     if (st || (st = ctx->note_capture())) return st;
     rlnc::SparseMatmulParams p{};

@@ -200,10 +200,11 @@ inline int bsj_waves(int n_out) { return n_out <= 8 ? 1 : n_out <= 16 ? 2 : 4; }
 
 int bsj_waves(int n_out, bool wide) { return wide && n_out > 32 ? 8 : bsj_waves(n_out); }
 
-// Whole 4 KiB column blocks of 16-byte-aligned operands; the ragged tail goes to the perm kernel.
+// Whole 4 KiB column blocks of 16-byte-aligned operands; the ragged tail goes to the perm kernel.  The tile assembly
+// adds the row strides to its row pointers as unsigned 32-bit numbers (bsj_tile.hpp), so they are in [0, 2^32) here.
 bool bsj_eligible(const MatmulParams &p, bool aligned) {
-    return aligned && p.width >= kBsjColBlock && p.n_out >= 4 && p.in_row < (int64_t(1) << 32) &&
-           p.out_row < (int64_t(1) << 32);
+    return aligned && p.width >= kBsjColBlock && p.n_out >= 4 && p.in_row >= 0 && p.in_row < (int64_t(1) << 32) &&
+           p.out_row >= 0 && p.out_row < (int64_t(1) << 32);
 }
 
 size_t bsj_scratch_bytes(const MatmulParams &p, bool wide) {
@@ -247,8 +248,10 @@ hipError_t bsj_shared_base(hipStream_t s, void *scratch, uint64_t &base) {
     return hipSuccess;
 }
 
-// The block-address stream of a bit-sliced jump product (one bsj_offset_kernel launch) and the launch geometry of its
-// whole 4 KiB column blocks (kernels.hpp BsjPlan)
+constexpr int kBsjOffsetObjects = 65535;  // objects per bsj_offset_kernel launch (blockIdx.y)
+
+// The block-address stream of a bit-sliced jump product (one bsj_offset_kernel launch per 65,535 objects) and the
+// launch geometry of its whole 4 KiB column blocks (kernels.hpp BsjPlan)
 hipError_t bsj_prepare(const MatmulParams &p, hipStream_t s, void *scratch, size_t scratch_bytes, bool share,
                        bool wide, BsjPlan &b) {
     b.full = (p.width / kBsjColBlock) * kBsjColBlock;
@@ -269,7 +272,7 @@ hipError_t bsj_prepare(const MatmulParams &p, hipStream_t s, void *scratch, size
     b.row_tiles = (p.n_out + tile_rows - 1) / tile_rows;
     b.col_blocks = int(b.full / kBsjColBlock);
     b.total = int64_t(p.n_obj) * b.row_tiles * b.col_blocks;
-    if (b.total > 0x7FFFFFFFLL || p.n_obj > 65535) return hipErrorInvalidValue;
+    if (b.total > 0x7FFFFFFFLL) return hipErrorInvalidValue;
     if (p.bsj_stream != nullptr && p.bsj_stream_rows == tile_rows && (p.bsj_stream_abs != 0) == abs) {
         // written already: by the small-object elimination (4-byte offsets) or by launch_bsj_stream ahead
         b.stream = const_cast<void *>(p.bsj_stream);
@@ -278,10 +281,19 @@ hipError_t bsj_prepare(const MatmulParams &p, hipStream_t s, void *scratch, size
     b.stream = scratch;
     const int64_t per_obj = int64_t(b.row_tiles) * p.n_in * tile_rows;
     if ((per_obj + 255) / 256 > 0x7FFFFFFFLL) return hipErrorInvalidValue;
-    const dim3 og(unsigned((per_obj + 255) / 256), unsigned(p.n_obj));
-    hipLaunchKernelGGL(abs ? &bsj_offset_kernel<true> : &bsj_offset_kernel<false>, og, dim3(256), 0, s, p.coef,
-                       p.coef_obj, p.coef_row, p.n_out, p.n_in, b.row_tiles, tile_rows, b.stream, base);  // !abs: base 0
-    return hipGetLastError();
+    // the object is the grid's y, which holds 65,535: more objects take one launch per range of that many, each on its
+    // own coefficients and its own part of the stream (the layout is the same as one launch's)
+    const int64_t entry = abs ? 8 : 4;
+    for (int o0 = 0; o0 < p.n_obj; o0 += kBsjOffsetObjects) {
+        const int c = std::min(kBsjOffsetObjects, p.n_obj - o0);
+        const dim3 og(unsigned((per_obj + 255) / 256), unsigned(c));
+        hipLaunchKernelGGL(abs ? &bsj_offset_kernel<true> : &bsj_offset_kernel<false>, og, dim3(256), 0, s,
+                           p.coef + int64_t(o0) * p.coef_obj, p.coef_obj, p.coef_row, p.n_out, p.n_in, b.row_tiles,
+                           tile_rows, static_cast<uint8_t *>(b.stream) + int64_t(o0) * per_obj * entry,
+                           base);  // !abs: base 0
+        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 static hipError_t launch_bsj(const MatmulParams &p, hipStream_t s, void *scratch, size_t scratch_bytes, int64_t &full,

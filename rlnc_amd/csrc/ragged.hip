@@ -254,7 +254,8 @@ __global__ __launch_bounds__(kThreads) void gf_matmul_perm_ragged_kernel(const R
 bool ragged_bsj_eligible(const uint8_t *in, const uint8_t *out, int64_t in_row, int64_t out_row, int64_t width,
                          int n_out, bool unaligned_ok) {
     return (unaligned_ok || (al16(in) && al16(out) && al16(in_row) && al16(out_row))) && width >= kBsjColBlock &&
-           n_out >= 4 && in_row < (int64_t(1) << 32) && out_row < (int64_t(1) << 32);
+           n_out >= 4 && in_row >= 0 && in_row < (int64_t(1) << 32) && out_row >= 0 &&
+           out_row < (int64_t(1) << 32);  // the tile assembly's unsigned 32-bit row strides (bsj_tile.hpp)
 }
 
 hipError_t launch_ragged_offsets(const RaggedObj *objs, int n, int64_t entries, void *stream, uint64_t base,

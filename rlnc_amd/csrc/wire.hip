@@ -145,7 +145,8 @@ int launch_pad(rlnc_context *ctx, const std::vector<PadDesc> &d) {
     int64_t max_blocks = 0;
     for (const auto &x : d) max_blocks = std::max<int64_t>(max_blocks, ((x.L + 15) / 16 * x.k + 255) / 256);
     if (max_blocks == 0) return RLNC_OK;
-    if (max_blocks > 0x7FFFFFFF || d.size() > 65535) return set_error(RLNC_ERR_INVALID_ARGUMENT, "pad batch too large");
+    if (max_blocks > 0x7FFFFFFF || d.size() > RLNC_PAD_BATCH_MAX)  // the descriptor is the grid's y
+        return set_error(RLNC_ERR_INVALID_ARGUMENT, "pad batch too large");
     void *dd = nullptr;
     int st = upload_table(ctx, d.data(), d.size() * sizeof(PadDesc), &dd);
     if (st) return st;

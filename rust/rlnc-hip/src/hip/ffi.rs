@@ -39,6 +39,8 @@ pub const RLNC_STATUS_PENDING: c_int = -1;
 pub const RLNC_STREAM_FORM_AUTO: c_int = 0;
 pub const RLNC_STREAM_FORM_WORKSPACE: c_int = 1;
 pub const RLNC_STREAM_FORM_LDS: c_int = 2;
+// the most descriptors one rlnc_pad_batch_device call takes
+pub const RLNC_PAD_BATCH_MAX: c_int = 65535;
 
 // ---- opaque handles ----
 #[repr(C)]
