@@ -71,7 +71,10 @@
  *     rows are renumbered to match, and the state is a fresh stream's after the kept pieces -- so m bounds the pieces
  *     an object holds, not the arrivals it sees, and a place is reused while its neighbours go on.
  *     rlnc_decode_stream_deliver (rlnc_amd/csrc/stream_deliver.hip) hands over the decoded data of the objects whose
- *     rank is k, chosen on the device, at the cost of those objects' products alone.  Not covered: the
+ *     rank is k, chosen on the device, at the cost of those objects' products alone.
+ *     rlnc_decode_stream_recode (rlnc_amd/csrc/stream_recode.hip) is the relay's call: every selected object that
+ *     holds a useful piece gets count recoded pieces over exactly its useful pieces -- the slots compact would keep --
+ *     found on the device, so a relay forwards without leaving the push -> deliver -> compact loop.  Not covered: the
  *     reference rank mode has no stream form (a context in mode 0 is refused).  Measured on one MI355X
  *     (profiles/r12_decode_stream.jsonl, profiles/r14_stream_lds.jsonl, profiles/r16_stream_compact.jsonl): see
  *     DESIGN.md §4.2.4.
@@ -582,6 +585,55 @@ int rlnc_decode_stream_deliver(rlnc_context *ctx, const void *state_dev, size_t 
                                size_t pieces_obj_stride, size_t k, size_t L, size_t m, size_t num_objects,
                                const int32_t *select_dev, uint8_t *decoded_dev, int32_t *object_status_dev,
                                int64_t *data_len_dev, void *plan_dev, size_t plan_bytes);
+
+/* Bytes of rlnc_decode_stream_recode's plan buffer: the expanded coefficients C [obj][count][m] and the block-address
+ * stream of the product (8 bytes per entry of ceil(count / tile rows) * tile rows x m coefficients per object, tile rows
+ * = 8, 16, 32 or 64 by count).  A multiple of 16, non-decreasing in count; 0 exactly where
+ * rlnc_decode_stream_state_bytes is 0 or count is outside [1, 4096].  Pure: needs no context and no GPU. */
+size_t rlnc_decode_stream_recode_plan_bytes(size_t k, size_t m, size_t count, size_t num_objects);
+/* Recodes for a relay from the pieces a stream's objects hold, found on the device: count recoded pieces per selected
+ * object, each a random combination of the object's useful pieces.  rank and done_o are taken as the last push or
+ * compaction left them (the context's stream orders the calls).  Let u_0 < ... < u_{r-1} be the slots below done_o
+ * whose status is Ok, r = rank: the list rlnc_decode_stream_compact keeps.  Pieces answered PieceNotUseful or
+ * ReceivedAllPieces are left out -- they add nothing to the span.  r_dev is uint8 [obj][count][k], the bytes
+ * rng.fill_bytes would draw (recoder.rs:131), supplied by the caller as in every other call here; out_dev is
+ * [obj][count][k+L], contiguous; status_dev int32 [obj]; used_dev int32 [obj], may be NULL.  Per object o:
+ *   unselected   (select_dev != NULL and select_dev[o] == 0) nothing of the object is written: no byte of out_dev[o],
+ *                neither status_dev[o] nor used_dev[o].
+ *   rank 0       (nothing pushed, or only zero vectors) status_dev[o] = NotEnoughPiecesToRecode, what Recoder::new
+ *                answers for no pieces; used_dev[o] = 0; no byte of out_dev[o] is written and no product work is done
+ *                (its workgroups return on reading the state).
+ *   rank r > 0   out_dev[o][i][0 .. k+L) = XOR over j < r of r_dev[o][i][j] * pieces[o][u_j][0 .. k+L) for i < count:
+ *                header and data are one linear map over the full piece, as in rlnc_recode_batch.  The bytes
+ *                r_dev[o][i][r .. k) are ignored.  status_dev[o] = RLNC_OK, used_dev[o] = r.  Byte for byte
+ *                Recoder::new over the useful pieces in arrival order followed by recode_with_buf with the random bytes
+ *                r_dev[o][i][0 .. r), count times.
+ * The state, the pieces, select_dev and r_dev are only read: a later push, compact or deliver continues unchanged.
+ * plan_dev is caller-owned scratch, 16-byte aligned and at least rlnc_decode_stream_recode_plan_bytes long; its
+ * contents after the call are unspecified.
+ * Columns.  A recoding object's product takes done_o source rows, read on the device: a useless slot below done_o is a
+ * zero column of the expanded coefficients, so the product costs done_o / r of the minimal count x r x (k+L) one.
+ * After rlnc_decode_stream_compact u_j = j and done_o = r: the minimal product.  A relay with many useless arrivals
+ * compacts, then recodes.
+ * Launches: at most four on the context's stream -- the expansion (a workgroup per object and 16 rows of C: numbers the Ok
+ * slots, writes C[o][i][u_j] = r_dev[o][i][j] and zero elsewhere below done_o into the plan, and status_dev and used_dev), the
+ * block-address streams of the recoding objects, the bit-sliced product over the whole 4 KiB column blocks of k+L (the
+ * program of the batch products, 8, 16, 32 or 64 rows a workgroup by count), a perm-multiply product over what that
+ * does not take ((k+L) mod 4096; everything for count < 4 or operands the program refuses).  The call never
+ * synchronises and grows no context workspace, so (push, recode) can be captured as a linear HIP graph -- after one
+ * eager recode or deliver on the device: the 32- and 64-row programs look up their block table once per device,
+ * synchronously, and a first such call inside a capture runs every column in the perm-multiply kernel instead (the
+ * same bytes, slower).
+ * Checks in deliver's order: a null handle RLNC_ERR_INVALID_ARGUMENT; k == 0 PieceCountZero; L == 0 PieceLengthZero;
+ * count == 0 or num_objects == 0 RLNC_OK, nothing launched; then the state and shape checks of push (rank mode 0, a
+ * buffer never initialised or initialised for another shape); pieces_obj_stride (0 = m*(k+L)) >= m*(k+L); pieces_dev,
+ * r_dev, out_dev and status_dev non-null; count <= 4096; plan_dev non-null, aligned and long enough; every launch
+ * within 2^31 - 1 workgroups.  Each failure is RLNC_ERR_INVALID_ARGUMENT, names the limit in rlnc_last_error and
+ * writes nothing.  Measurements: DESIGN.md §4.2.4, "Recoding". */
+int rlnc_decode_stream_recode(rlnc_context *ctx, const void *state_dev, size_t state_bytes, const uint8_t *pieces_dev,
+                              size_t pieces_obj_stride, size_t k, size_t L, size_t m, size_t num_objects,
+                              const int32_t *select_dev, const uint8_t *r_dev, size_t count, uint8_t *out_dev,
+                              int32_t *status_dev, int32_t *used_dev, void *plan_dev, size_t plan_bytes);
 
 /* ---- wire formats on the device ------------------------------------------------------------
  * Encoder::new's padded image (encoder.rs:85-106, BOUNDARY_MARKER consts.rs:5) built by a kernel from a byte

@@ -163,6 +163,9 @@ _SIGS = {
     "rlnc_decode_stream_deliver_plan_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t]),
     "rlnc_decode_stream_deliver": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                              C.c_size_t, vp, vp, vp, vp, vp, C.c_size_t]),
+    "rlnc_decode_stream_recode_plan_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "rlnc_decode_stream_recode": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
+                                            C.c_size_t, vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]),
     "rlnc_recode_batch": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "rlnc_encode_batch_sparse": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t,
                                            vp]),

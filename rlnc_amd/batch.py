@@ -456,6 +456,15 @@ def stream_deliver_plan_bytes(k: int, m: int, num_objects: int) -> int:
     return int(load().rlnc_decode_stream_deliver_plan_bytes(k, m, num_objects))
 
 
+def stream_recode_plan_bytes(k: int, m: int, count: int, num_objects: int) -> int:
+    """Device bytes of DecodeStream.recode's plan buffer for count recoded pieces per object
+    (rlnc_decode_stream_recode_plan_bytes): a multiple of 16, non-decreasing in count, 0 exactly where state_bytes is 0
+    or count is outside [1, 4096].  Needs no GPU."""
+    from ._lib import load
+
+    return int(load().rlnc_decode_stream_recode_plan_bytes(k, m, count, num_objects))
+
+
 class DecodeStream:
     """The true-rank decoder state of num_objects objects (generation size k, m piece slots each) kept on the device
     between calls.  Slot t of object o is pieces[o][t] of the caller's pieces [obj][m][k+L] tensor; the caller fills
@@ -481,6 +490,7 @@ class DecodeStream:
         self._T = None
         self._rank = None
         self._plan = None
+        self._recode_plan = None
         c = _ctx_for(self.state, self.ctx)
         check(c.lib.rlnc_decode_stream_init(c.h, C.c_void_p(self.state.data_ptr()), nbytes, self.k, self.m,
                                             self.num_objects), c.lib)
@@ -589,3 +599,46 @@ class DecodeStream:
                                                self.num_objects, sel, C.c_void_p(decoded.data_ptr()), os_,
                                                C.c_void_p(data_len.data_ptr()), C.c_void_p(self._plan.data_ptr()),
                                                self._plan.numel()), c.lib)
+
+    def recode_reserve(self, count: int) -> None:
+        """Grows the stream's recode plan buffer to what recode() of count pieces per object needs (never shrinks it).
+        recode() calls this itself; a buffer cannot grow inside a capture, so a graph's largest count is reserved, or
+        recoded once eagerly, before capturing."""
+        import torch
+
+        nbytes = stream_recode_plan_bytes(self.k, self.m, int(count), self.num_objects)
+        assert nbytes > 0, f"a stream recode takes 1 <= count <= 4096: {count}"
+        if self._recode_plan is None or self._recode_plan.numel() < nbytes:
+            assert not torch.cuda.is_current_stream_capturing(), \
+                "the recode's plan buffer cannot grow inside a capture: recode_reserve(count) before capturing"
+            self._recode_plan = torch.empty(nbytes, dtype=torch.uint8, device=self.state.device)
+            assert self._recode_plan.data_ptr() % 16 == 0
+
+    def recode(self, pieces, r, out, status, used=None, select=None) -> None:
+        """The relay's call (rlnc_decode_stream_recode): count = r.shape[1] recoded pieces per selected object over the
+        useful pieces it holds -- the slots below done_o whose status is Ok, u_0 < ... < u_{rank-1}, the ones compact()
+        keeps -- found on the device.  r uint8 [obj][count][k], the random bytes (row i's first rank bytes are used);
+        out uint8 [obj][count][k+L]: out[o][i] = sum_j r[o][i][j] * pieces[o][u_j], header and data alike; status int32
+        [obj]: Ok, or NotEnoughPiecesToRecode (6) for an object of rank 0, of which no byte of out[o] is written; used
+        int32 [obj], optional: the rank; an object with select[o] == 0 (int32 [obj], optional) gets nothing written at
+        all.  The state and the pieces are only read.  The product takes done_o source rows: after compact() that is the
+        rank, the minimum.  The stream owns the plan buffer and grows it for a larger count, eagerly and never inside a
+        capture (recode_reserve): call recode once with the largest count before capturing (push, recode) into a graph
+        -- that call also looks up the 32- and 64-row programs' block table, which a capture cannot."""
+        L, obj_stride = self._pieces(pieces)
+        _chk(r)
+        assert r.dim() == 3 and tuple(r.shape) == (self.num_objects, r.shape[1], self.k) and r.shape[1] >= 1, \
+            (tuple(r.shape), self.num_objects, self.k)
+        count = int(r.shape[1])
+        _chk(out, (self.num_objects, count, self.k + L))
+        n = (self.num_objects,)
+        st = self._i32(status, n, "status")
+        us = self._i32(used, n, "used") if used is not None else None
+        sel = self._i32(select, n, "select") if select is not None else None
+        self.recode_reserve(count)
+        c = _ctx_for(self.state, self.ctx)
+        check(c.lib.rlnc_decode_stream_recode(c.h, C.c_void_p(self.state.data_ptr()), self.state.numel(),
+                                              C.c_void_p(pieces.data_ptr()), obj_stride, self.k, L, self.m,
+                                              self.num_objects, sel, C.c_void_p(r.data_ptr()), count,
+                                              C.c_void_p(out.data_ptr()), st, us,
+                                              C.c_void_p(self._recode_plan.data_ptr()), self._recode_plan.numel()), c.lib)

@@ -2,8 +2,8 @@
 // true-rank decoder state of many objects in a caller-owned device buffer, pushed forward as pieces arrive
 // (rank_large.hip in its stream form, rank_large_kernels.hpp; for generations that fit LDS also the one-launch form of
 // rank_stream.hip, rank_stream_kernels.hpp), compacted in place (rank_compact.hip, rank_compact_kernels.hpp), its
-// finished objects delivered (stream_deliver.hip, stream_deliver_kernels.hpp), and the registry of initialised state
-// buffers.  The state buffer itself: rank_state.hpp.
+// finished objects delivered (stream_deliver.hip, stream_deliver_kernels.hpp), the pieces it holds recoded for a relay
+// (stream_recode.hip, stream_recode_kernels.hpp), and the registry of initialised state buffers.  The state buffer itself: rank_state.hpp.
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -12,6 +12,7 @@
 #include "rank_compact_kernels.hpp"
 #include "rank_stream_kernels.hpp"
 #include "stream_deliver_kernels.hpp"
+#include "stream_recode_kernels.hpp"
 
 using namespace rlnc::eng;
 
@@ -221,6 +222,53 @@ int rlnc_decode_stream_deliver(rlnc_context *ctx, const void *state, size_t stat
                          "launch: deliver fewer objects per call", nobj, k, m, L);
     if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
     HIP_TRY(rlnc::launch_stream_deliver(p, state, state_bytes, rlnc::unaligned_vector_ok(), ctx->stream));
+    return RLNC_OK;
+}
+
+size_t rlnc_decode_stream_recode_plan_bytes(size_t k, size_t m, size_t count, size_t nobj) {
+    return rlnc::stream_recode_plan_bytes(k, m, count, nobj);
+}
+
+int rlnc_decode_stream_recode(rlnc_context *ctx, const void *state, size_t state_bytes, const uint8_t *pieces,
+                              size_t obj_stride, size_t k, size_t L, size_t m, size_t nobj, const int32_t *select,
+                              const uint8_t *r, size_t count, uint8_t *out, int32_t *status_dev, int32_t *used_dev,
+                              void *plan, size_t plan_bytes) {
+    CHECK_ARG(ctx != nullptr);
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    if (L == 0) return RLNC_ERR_PIECE_LENGTH_ZERO;
+    if (count == 0 || nobj == 0) return RLNC_OK;
+    int st = stream_args(ctx, state, state_bytes, k, m, nobj);
+    if (st || (st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))) return st;
+    CHECK_ARG(L <= (size_t(1) << 40));  // m * (k + L) and count * (k + L) stay far inside 64 bits
+    if (obj_stride == 0) obj_stride = m * (k + L);
+    CHECK_ARG(obj_stride >= m * (k + L));
+    CHECK_ARG(pieces != nullptr && r != nullptr && out != nullptr && status_dev != nullptr);
+    if (count > size_t(rlnc::kRecodeMaxCount))
+        return set_error(RLNC_ERR_INVALID_ARGUMENT, "a stream recode takes 1 <= count <= %d recoded pieces per object "
+                         "(count=%zu): recode in several calls", rlnc::kRecodeMaxCount, count);
+    const size_t need = rlnc::stream_recode_plan_bytes(k, m, count, nobj);
+    if (plan == nullptr || (reinterpret_cast<uintptr_t>(plan) & 15) != 0 || plan_bytes < need)
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "the recode's plan buffer must be non-null, 16-byte aligned and at least "
+                         "rlnc_decode_stream_recode_plan_bytes(k=%zu, m=%zu, count=%zu, %zu objects) = %zu bytes long "
+                         "(%p, %zu bytes)", k, m, count, nobj, need, plan, plan_bytes);
+    rlnc::RecodeParams p{};
+    p.pieces = pieces;
+    p.obj_stride = int64_t(obj_stride);
+    p.k = int(k), p.m = int(m), p.n_obj = int(nobj), p.count = int(count);
+    p.L = int64_t(L);
+    p.select = select;
+    p.r = r;
+    p.out = out;
+    p.status = status_dev;
+    p.used = used_dev;
+    p.plan = plan;
+    if (!rlnc::stream_recode_fits(p))
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "a recode of %zu objects of k=%zu, m=%zu, L=%zu, count=%zu needs more than 2^31 - 1 workgroups in "
+                         "one launch: recode fewer objects per call", nobj, k, m, L, count);
+    if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
+    HIP_TRY(rlnc::launch_stream_recode(p, state, state_bytes, rlnc::unaligned_vector_ok(), ctx->stream));
     return RLNC_OK;
 }
 

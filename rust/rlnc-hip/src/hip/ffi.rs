@@ -560,6 +560,26 @@ unsafe extern "C" {
         plan_dev: *mut c_void,
         plan_bytes: usize,
     ) -> c_int;
+    pub fn rlnc_decode_stream_recode_plan_bytes(k: usize, m: usize, count: usize, num_objects: usize) -> usize;
+    pub fn rlnc_decode_stream_recode(
+        ctx: *mut rlnc_context,
+        state_dev: *const c_void,
+        state_bytes: usize,
+        pieces_dev: *const u8,
+        pieces_obj_stride: usize,
+        k: usize,
+        L: usize,
+        m: usize,
+        num_objects: usize,
+        select_dev: *const i32,
+        r_dev: *const u8,
+        count: usize,
+        out_dev: *mut u8,
+        status_dev: *mut i32,
+        used_dev: *mut i32,
+        plan_dev: *mut c_void,
+        plan_bytes: usize,
+    ) -> c_int;
 
     // wire formats on the device
     pub fn rlnc_padded_piece_byte_len(data_len: usize, k: usize) -> usize;
