@@ -74,7 +74,10 @@
  *     rank is k, chosen on the device, at the cost of those objects' products alone.
  *     rlnc_decode_stream_recode (rlnc_amd/csrc/stream_recode.hip) is the relay's call: every selected object that
  *     holds a useful piece gets count recoded pieces over exactly its useful pieces -- the slots compact would keep --
- *     found on the device, so a relay forwards without leaving the push -> deliver -> compact loop.  Not covered: the
+ *     found on the device, so a relay forwards without leaving the push -> deliver -> compact loop.
+ *     rlnc_decode_stream_accept (rlnc_amd/csrc/stream_accept.hip) is the step before the push: arrivals for many
+ *     objects, interleaved in one staging buffer, go into their objects' next free slots in arrival order, with the
+ *     slot decided on the device from avail and the rank, so the loop needs no host decision.  Not covered: the
  *     reference rank mode has no stream form (a context in mode 0 is refused).  Measured on one MI355X
  *     (profiles/r12_decode_stream.jsonl, profiles/r14_stream_lds.jsonl, profiles/r16_stream_compact.jsonl): see
  *     DESIGN.md §4.2.4.
@@ -634,6 +637,66 @@ int rlnc_decode_stream_recode(rlnc_context *ctx, const void *state_dev, size_t s
                               size_t pieces_obj_stride, size_t k, size_t L, size_t m, size_t num_objects,
                               const int32_t *select_dev, const uint8_t *r_dev, size_t count, uint8_t *out_dev,
                               int32_t *status_dev, int32_t *used_dev, void *plan_dev, size_t plan_bytes);
+
+/* What rlnc_decode_stream_accept answers in slot_dev for an arrival that it did not place. */
+#define RLNC_ACCEPT_NO_ROOM (-1)   /* the object's m slots are filled */
+#define RLNC_ACCEPT_NO_OBJECT (-2) /* object id outside [0, num_objects) */
+#define RLNC_ACCEPT_FINISHED (-3)  /* state_dev given and the object's rank is k */
+#define RLNC_ACCEPT_ABSENT (-4)    /* index at or beyond the device count */
+/* Bytes of rlnc_decode_stream_accept's plan buffer: five int32 arrays, four of n entries (an arrival's rank among the
+ * equal ids of its chunk of 1,024, its chunk's first equal id, that id's count in the chunk, the slot the chunk's first
+ * one takes) and one of num_objects (the next free slot), each rounded up to 16 bytes.  A multiple
+ * of 16, non-decreasing in both arguments; 0 for n == 0, n > 1,048,576 and num_objects == 0 (or beyond 2^31 - 1).
+ * Pure: needs no context and no GPU. */
+size_t rlnc_decode_stream_accept_plan_bytes(size_t n, size_t num_objects);
+/* Accepts mixed arrivals into their objects' slots, decided on the device: the receive loop's first call,
+ * compact(answered = avail) -> accept(arrivals, object, avail) -> push(avail) -> deliver.  arrivals_dev holds n full
+ * coded pieces of k + L bytes for many objects, interleaved as they came: arrival i starts at arrivals_dev + i *
+ * arrival_stride (0 = k + L), at any byte address, and belongs to object object_dev[i] (int32 [n]).  count_dev may be
+ * NULL; otherwise it points to one device int32, read by the rank and the base launch and written by neither, and the
+ * call takes the first n' = min(max(*count_dev, 0), n)
+ * arrivals (NULL: n' = n), so that a captured call replays with another number of arrivals each time.  n is the
+ * host-known capacity, at most 1,048,576: a receiver with more arrivals calls again.  avail_dev (int32 [num_objects]) is
+ * the array push takes, and what rlnc_decode_stream_compact writes as answered_dev goes in as it is.  Per object o:
+ *   let a = min(max(avail_dev[o], 0), m), read once, and i_0 < i_1 < ... the arrivals below n' whose id is o, in
+ *   arrival order (the assignment is stable: no slot is claimed with an atomic).
+ *   finished     (state_dev != NULL and rank_o == k, the rank as the last push or compaction left it: the context's
+ *                stream orders the calls) slot_dev[i_j] = RLNC_ACCEPT_FINISHED for every j; no byte of the object's
+ *                pieces is written and avail_dev[o] keeps its value; refused_dev[o] = 0.
+ *   else         arrival i_j goes to slot a + j while a + j < m: all k + L bytes are copied to pieces_dev[o][a + j] and
+ *                slot_dev[i_j] = a + j.  The arrivals from j = m - a on get RLNC_ACCEPT_NO_ROOM and are not copied.
+ *                avail_dev[o] = min(a + count_o, m); refused_dev[o] = the number of its arrivals that found no room.  An
+ *                object with no arrival in the call still has avail_dev[o] rewritten with a, and refused_dev[o] = 0.
+ * An id outside [0, num_objects) gets RLNC_ACCEPT_NO_OBJECT, an index in [n', n) RLNC_ACCEPT_ABSENT.  slot_dev (int32
+ * [n]) and refused_dev (int32 [num_objects]) may each be NULL; when given, every entry is written.  state_dev == NULL:
+ * no finished filter, the registry of initialised state buffers is not consulted and state_bytes is ignored (k and m
+ * still say where a piece goes).
+ * Equivalence: after the call the pieces and avail_dev hold exactly what a host loop of one copy per arrival into
+ * pieces[o][filled[o]++] leaves after the same arrivals in the same order, with the arrivals beyond m dropped; a
+ * following push(avail_dev) answers as a decoder fed those pieces in arrival order.
+ * Footprint.  Written: the k + L bytes of every slot assigned in this call; avail_dev[0 .. num_objects) (but a finished
+ * object's entry); slot_dev[0 .. n); refused_dev[0 .. num_objects); the plan buffer.  Never written: the slots below a
+ * or at and beyond the new avail; the bytes between m*(k+L) and the object stride; the arrivals, object_dev, count_dev;
+ * any byte of the state.  plan_dev is caller-owned scratch, 16-byte aligned and at least
+ * rlnc_decode_stream_accept_plan_bytes long; its contents after the call are unspecified.
+ * Launches: three on the context's stream -- rank (a workgroup per 1,024 arrivals: every arrival's place among the equal
+ * ids of its chunk), base (one workgroup: the chunks in order, ceil(n' / 1024) dependent steps, the call's only serial
+ * part; avail_dev and refused_dev), move (arrival x 4 KiB of a piece: the copy, 16-byte accesses at any byte address
+ * where rlnc_device_unaligned_vector_access is 1, single bytes otherwise; slot_dev).  The call never synchronises and
+ * grows no context workspace, so (compact, accept, push, deliver) can be captured as a linear HIP graph.
+ * Checks in the order of push and deliver: a null handle RLNC_ERR_INVALID_ARGUMENT; k == 0 PieceCountZero; L == 0
+ * PieceLengthZero; n == 0 or num_objects == 0 RLNC_OK, nothing launched; with state_dev the state and shape checks of
+ * push (rank mode 0, a buffer never initialised or initialised for another shape); 1 <= m <= 8192 and k <= 4096 even
+ * without a state; n <= 1,048,576; L <= 2^40; arrival_stride 0 or in [k + L, 2^42]; pieces_obj_stride (0 = m*(k+L))
+ * >= m*(k+L); arrivals_dev, object_dev, pieces_dev and avail_dev non-null; plan_dev non-null, aligned and long enough; every launch
+ * within 2^31 - 1 workgroups.  Each failure is RLNC_ERR_INVALID_ARGUMENT, names the limit in rlnc_last_error and
+ * writes nothing.  Measurements: DESIGN.md §4.2.4, "Accepting arrivals". */
+int rlnc_decode_stream_accept(rlnc_context *ctx, const void *state_dev, size_t state_bytes,
+                              const uint8_t *arrivals_dev, size_t arrival_stride, const int32_t *object_dev,
+                              size_t n, const int32_t *count_dev,
+                              uint8_t *pieces_dev, size_t pieces_obj_stride, size_t k, size_t L, size_t m,
+                              size_t num_objects, int32_t *avail_dev, int32_t *slot_dev, int32_t *refused_dev,
+                              void *plan_dev, size_t plan_bytes);
 
 /* ---- wire formats on the device ------------------------------------------------------------
  * Encoder::new's padded image (encoder.rs:85-106, BOUNDARY_MARKER consts.rs:5) built by a kernel from a byte

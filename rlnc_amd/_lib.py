@@ -67,6 +67,11 @@ RLNC_DECODE_PATH_DEVICE_ANY = 7
 RLNC_DECODE_PATH_LARGE = 8
 # a decode stream's slot that no push has answered yet (rlnc_decode_stream_snapshot)
 RLNC_STATUS_PENDING = -1
+# what rlnc_decode_stream_accept answers for an arrival it did not place
+RLNC_ACCEPT_NO_ROOM = -1
+RLNC_ACCEPT_NO_OBJECT = -2
+RLNC_ACCEPT_FINISHED = -3
+RLNC_ACCEPT_ABSENT = -4
 # which kernels a decode stream's push runs (rlnc_set_stream_form)
 RLNC_STREAM_FORM_AUTO = 0
 RLNC_STREAM_FORM_WORKSPACE = 1
@@ -166,6 +171,9 @@ _SIGS = {
     "rlnc_decode_stream_recode_plan_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
     "rlnc_decode_stream_recode": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                             C.c_size_t, vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]),
+    "rlnc_decode_stream_accept_plan_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t]),
+    "rlnc_decode_stream_accept": (C.c_int, [vp, vp, C.c_size_t, vp, C.c_size_t, vp, C.c_size_t, vp, vp, C.c_size_t,
+                                            C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, vp, vp, C.c_size_t]),
     "rlnc_recode_batch": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp]),
     "rlnc_encode_batch_sparse": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, vp, C.c_size_t, C.c_size_t,
                                            vp]),

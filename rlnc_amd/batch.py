@@ -465,6 +465,15 @@ def stream_recode_plan_bytes(k: int, m: int, count: int, num_objects: int) -> in
     return int(load().rlnc_decode_stream_recode_plan_bytes(k, m, count, num_objects))
 
 
+def stream_accept_plan_bytes(n: int, num_objects: int) -> int:
+    """Device bytes of DecodeStream.accept's plan buffer for up to n arrivals per call
+    (rlnc_decode_stream_accept_plan_bytes): a multiple of 16, non-decreasing in both arguments, 0 for n = 0,
+    n > 1,048,576 and num_objects = 0.  Needs no GPU."""
+    from ._lib import load
+
+    return int(load().rlnc_decode_stream_accept_plan_bytes(n, num_objects))
+
+
 class DecodeStream:
     """The true-rank decoder state of num_objects objects (generation size k, m piece slots each) kept on the device
     between calls.  Slot t of object o is pieces[o][t] of the caller's pieces [obj][m][k+L] tensor; the caller fills
@@ -491,6 +500,7 @@ class DecodeStream:
         self._rank = None
         self._plan = None
         self._recode_plan = None
+        self._accept_plan = None
         c = _ctx_for(self.state, self.ctx)
         check(c.lib.rlnc_decode_stream_init(c.h, C.c_void_p(self.state.data_ptr()), nbytes, self.k, self.m,
                                             self.num_objects), c.lib)
@@ -642,3 +652,53 @@ class DecodeStream:
                                               self.num_objects, sel, C.c_void_p(r.data_ptr()), count,
                                               C.c_void_p(out.data_ptr()), st, us,
                                               C.c_void_p(self._recode_plan.data_ptr()), self._recode_plan.numel()), c.lib)
+
+    def accept_reserve(self, n: int) -> None:
+        """Grows the stream's accept plan buffer to what accept() of up to n arrivals needs (never shrinks it).
+        accept() calls this itself; a buffer cannot grow inside a capture, so a graph's largest n is reserved, or
+        accepted once eagerly, before capturing."""
+        import torch
+
+        nbytes = stream_accept_plan_bytes(int(n), self.num_objects)
+        assert nbytes > 0, f"a stream accept takes 1 <= n <= 1,048,576 arrivals per call: {n}"
+        if self._accept_plan is None or self._accept_plan.numel() < nbytes:
+            assert not torch.cuda.is_current_stream_capturing(), \
+                "the accept's plan buffer cannot grow inside a capture: accept_reserve(n) before capturing"
+            self._accept_plan = torch.empty(nbytes, dtype=torch.uint8, device=self.state.device)
+            assert self._accept_plan.data_ptr() % 16 == 0
+
+    def accept(self, arrivals, objects, pieces, avail, slot=None, refused=None, count=None, finished=False) -> None:
+        """The step before push (rlnc_decode_stream_accept): mixed arrivals go into their objects' next free slots in
+        arrival order, decided on the device.  arrivals uint8 [n][k+L] on the device, stride(1) == 1 and any row stride
+        of at least k + L, at any byte address; objects int32 [n], arrival i's object; avail int32 [obj], read and
+        rewritten: arrival j of object o in the call goes to slot a + j of pieces[o], a = avail[o] clamped to [0, m],
+        and avail[o] becomes min(a + its arrivals, m), what push takes next.  slot int32 [n], optional: the slot of
+        each arrival, or RLNC_ACCEPT_NO_ROOM (-1) from slot m on, RLNC_ACCEPT_NO_OBJECT (-2) for an id outside [0, obj),
+        RLNC_ACCEPT_FINISHED (-3), RLNC_ACCEPT_ABSENT (-4) for an index at or beyond count; refused int32 [obj],
+        optional: the object's arrivals that found no room.  count int32 [1] on the device, optional: only the first
+        min(max(count, 0), n) arrivals are taken, so a captured call replays with another number each time.
+        finished=True passes the stream's state: the arrivals of an object whose rank is k are answered
+        RLNC_ACCEPT_FINISHED, nothing of it is written and its avail keeps its value.  The stream owns the plan buffer
+        and grows it for a larger n, eagerly and never inside a capture (accept_reserve)."""
+        import torch
+
+        L, obj_stride = self._pieces(pieces)
+        S = self.k + L
+        assert arrivals.is_cuda and arrivals.dtype == torch.uint8 and arrivals.dim() == 2 and arrivals.shape[1] == S, \
+            (tuple(arrivals.shape), S)
+        n = int(arrivals.shape[0])
+        assert n >= 1 and (S == 1 or arrivals.stride(1) == 1) and (n == 1 or arrivals.stride(0) >= S), arrivals.stride()
+        arrival_stride = int(arrivals.stride(0)) if n > 1 else S
+        ob = self._i32(objects, (n,), "objects")
+        av = self._i32(avail, (self.num_objects,), "avail")
+        sl = self._i32(slot, (n,), "slot") if slot is not None else None
+        rf = self._i32(refused, (self.num_objects,), "refused") if refused is not None else None
+        ct = self._i32(count, (1,), "count") if count is not None else None
+        self.accept_reserve(n)
+        c = _ctx_for(self.state, self.ctx)
+        check(c.lib.rlnc_decode_stream_accept(c.h, C.c_void_p(self.state.data_ptr()) if finished else None,
+                                              self.state.numel() if finished else 0,
+                                              C.c_void_p(arrivals.data_ptr()), arrival_stride, ob, n, ct,
+                                              C.c_void_p(pieces.data_ptr()), obj_stride, self.k, L, self.m,
+                                              self.num_objects, av, sl, rf,
+                                              C.c_void_p(self._accept_plan.data_ptr()), self._accept_plan.numel()), c.lib)

@@ -3,7 +3,8 @@
 // (rank_large.hip in its stream form, rank_large_kernels.hpp; for generations that fit LDS also the one-launch form of
 // rank_stream.hip, rank_stream_kernels.hpp), compacted in place (rank_compact.hip, rank_compact_kernels.hpp), its
 // finished objects delivered (stream_deliver.hip, stream_deliver_kernels.hpp), the pieces it holds recoded for a relay
-// (stream_recode.hip, stream_recode_kernels.hpp), and the registry of initialised state buffers.  The state buffer itself: rank_state.hpp.
+// (stream_recode.hip, stream_recode_kernels.hpp), mixed arrivals accepted into their slots (stream_accept.hip,
+// stream_accept_kernels.hpp), and the registry of initialised state buffers.  The state buffer itself: rank_state.hpp.
 #include <mutex>
 #include <tuple>
 #include <vector>
@@ -11,6 +12,7 @@
 #include "context.hpp"
 #include "rank_compact_kernels.hpp"
 #include "rank_stream_kernels.hpp"
+#include "stream_accept_kernels.hpp"
 #include "stream_deliver_kernels.hpp"
 #include "stream_recode_kernels.hpp"
 
@@ -269,6 +271,65 @@ int rlnc_decode_stream_recode(rlnc_context *ctx, const void *state, size_t state
                          "one launch: recode fewer objects per call", nobj, k, m, L, count);
     if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
     HIP_TRY(rlnc::launch_stream_recode(p, state, state_bytes, rlnc::unaligned_vector_ok(), ctx->stream));
+    return RLNC_OK;
+}
+
+size_t rlnc_decode_stream_accept_plan_bytes(size_t n, size_t nobj) { return rlnc::stream_accept_plan_bytes(n, nobj); }
+
+int rlnc_decode_stream_accept(rlnc_context *ctx, const void *state, size_t state_bytes, const uint8_t *arrivals,
+                              size_t arrival_stride, const int32_t *object, size_t n, const int32_t *count,
+                              uint8_t *pieces, size_t obj_stride, size_t k, size_t L, size_t m, size_t nobj,
+                              int32_t *avail, int32_t *slot_dev, int32_t *refused_dev, void *plan, size_t plan_bytes) {
+    CHECK_ARG(ctx != nullptr);
+    if (k == 0) return RLNC_ERR_PIECE_COUNT_ZERO;
+    if (L == 0) return RLNC_ERR_PIECE_LENGTH_ZERO;
+    if (n == 0 || nobj == 0) return RLNC_OK;
+    int st;
+    if (state != nullptr &&
+        ((st = stream_args(ctx, state, state_bytes, k, m, nobj)) || (st = stream_check(state, StreamKey{ctx->device, k, m, nobj}))))
+        return st;
+    if (m == 0 || m > size_t(rlnc::kLargeMaxM) || k > size_t(rlnc::kLargeMaxK) || nobj > 0x7FFFFFFF)
+        return set_error(RLNC_ERR_INVALID_ARGUMENT, "an accept takes k <= %d, 1 <= m <= %d and fewer than 2^31 objects "
+                         "(k=%zu, m=%zu, %zu objects)", rlnc::kLargeMaxK, rlnc::kLargeMaxM, k, m, nobj);
+    if (n > size_t(rlnc::kAcceptMaxArrivals))
+        return set_error(RLNC_ERR_INVALID_ARGUMENT, "an accept takes n <= %d arrivals (n=%zu): accept in several calls",
+                         rlnc::kAcceptMaxArrivals, n);
+    if (L > (size_t(1) << 40))  // m * (k + L) and n * (k + L) stay far inside 64 bits
+        return set_error(RLNC_ERR_INVALID_ARGUMENT, "an accept takes L <= 2^40 bytes (L=%zu)", L);
+    if (arrival_stride == 0) arrival_stride = k + L;
+    if (arrival_stride < k + L || arrival_stride > (size_t(1) << 42))  // n * arrival_stride stays inside 64 bits
+        return set_error(RLNC_ERR_INVALID_ARGUMENT, "arrival_stride must be 0 or lie in [k + L, 2^42] = [%zu, %zu] "
+                         "(arrival_stride=%zu)", k + L, size_t(1) << 42, arrival_stride);
+    if (obj_stride == 0) obj_stride = m * (k + L);
+    CHECK_ARG(obj_stride >= m * (k + L));
+    CHECK_ARG(arrivals != nullptr && object != nullptr && pieces != nullptr && avail != nullptr);
+    const size_t need = rlnc::stream_accept_plan_bytes(n, nobj);
+    if (plan == nullptr || (reinterpret_cast<uintptr_t>(plan) & 15) != 0 || plan_bytes < need)
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "the accept's plan buffer must be non-null, 16-byte aligned and at least "
+                         "rlnc_decode_stream_accept_plan_bytes(n=%zu, %zu objects) = %zu bytes long (%p, %zu bytes)",
+                         n, nobj, need, plan, plan_bytes);
+    rlnc::AcceptParams p{};
+    p.arrivals = arrivals;
+    p.arrival_stride = int64_t(arrival_stride);
+    p.object = object;
+    p.count = count;
+    p.n = int(n);
+    p.pieces = pieces;
+    p.obj_stride = int64_t(obj_stride);
+    p.piece = int64_t(k + L);
+    p.k = int(k), p.m = int(m), p.n_obj = int(nobj);
+    p.avail = avail;
+    p.slot = slot_dev;
+    p.refused = refused_dev;
+    p.plan = plan;
+    if (!rlnc::stream_accept_fits(p))
+        return set_error(RLNC_ERR_INVALID_ARGUMENT,
+                         "an accept of n=%zu arrivals of k + L = %zu bytes needs more than 2^31 - 1 workgroups in one "
+                         "launch (n x floor((k + L) / %d)): accept fewer arrivals per call", n, k + L,
+                         rlnc::kAcceptColChunk);
+    if ((st = ctx->activate()) || (st = ctx->note_capture())) return st;
+    HIP_TRY(rlnc::launch_stream_accept(p, state, state_bytes, rlnc::unaligned_vector_ok(), ctx->stream));
     return RLNC_OK;
 }
 

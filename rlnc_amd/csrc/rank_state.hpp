@@ -1,7 +1,7 @@
 // rank_state.hpp — the per-object state buffer of the true-rank elimination beyond LDS and of decode streams (internal
 // to librlnc_hip): limits, layout, the four state words and their protocol, the check of a caller's buffer.  The
 // launches on it: rank_large_kernels.hpp, rank_stream_kernels.hpp (the LDS push), rank_compact_kernels.hpp,
-// stream_deliver_kernels.hpp and stream_recode_kernels.hpp (read only).
+// stream_deliver_kernels.hpp, stream_recode_kernels.hpp and stream_accept_kernels.hpp (read only).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -78,6 +78,8 @@ enum StateWord : int {
 //   tail and scan                                            stream snapshot)
 //   recode expand, offsets,   r                 r            no word written (stream_recode.hip); the expand launch reads
 //   product and tail                                         St[0 .. done) too and keeps its numbering in LDS
+//   accept base               r                              no word written (stream_accept.hip): rank == k is the
+//                                                            finished filter; the rank and move launches read no word
 //   stream init               w        w        w      w     all 0
 //   stream latch                                r      w     the target rule; no later launch of the push reads avail
 //   stream reduce             r                 r      r     its block: slots done .. min(done + B, target) - 1

@@ -35,6 +35,11 @@ pub const RLNC_DECODE_PATH_DEVICE_ANY: c_int = 7;
 pub const RLNC_DECODE_PATH_LARGE: c_int = 8;
 // a decode stream's slot that no push has answered yet (rlnc_decode_stream_snapshot)
 pub const RLNC_STATUS_PENDING: c_int = -1;
+// what rlnc_decode_stream_accept answers for an arrival it did not place
+pub const RLNC_ACCEPT_NO_ROOM: c_int = -1;
+pub const RLNC_ACCEPT_NO_OBJECT: c_int = -2;
+pub const RLNC_ACCEPT_FINISHED: c_int = -3;
+pub const RLNC_ACCEPT_ABSENT: c_int = -4;
 // which kernels a decode stream's push runs (rlnc_set_stream_form)
 pub const RLNC_STREAM_FORM_AUTO: c_int = 0;
 pub const RLNC_STREAM_FORM_WORKSPACE: c_int = 1;
@@ -577,6 +582,28 @@ unsafe extern "C" {
         out_dev: *mut u8,
         status_dev: *mut i32,
         used_dev: *mut i32,
+        plan_dev: *mut c_void,
+        plan_bytes: usize,
+    ) -> c_int;
+    pub fn rlnc_decode_stream_accept_plan_bytes(n: usize, num_objects: usize) -> usize;
+    pub fn rlnc_decode_stream_accept(
+        ctx: *mut rlnc_context,
+        state_dev: *const c_void,
+        state_bytes: usize,
+        arrivals_dev: *const u8,
+        arrival_stride: usize,
+        object_dev: *const i32,
+        n: usize,
+        count_dev: *const i32,
+        pieces_dev: *mut u8,
+        pieces_obj_stride: usize,
+        k: usize,
+        L: usize,
+        m: usize,
+        num_objects: usize,
+        avail_dev: *mut i32,
+        slot_dev: *mut i32,
+        refused_dev: *mut i32,
         plan_dev: *mut c_void,
         plan_bytes: usize,
     ) -> c_int;
