@@ -388,6 +388,60 @@ int rlnc_encode_batch_prepare(rlnc_context *ctx, const uint8_t *src_dev, size_t 
                               size_t plan_bytes);
 int rlnc_encode_batch_data_planned(rlnc_context *ctx, const uint8_t *src_dev, size_t k, size_t L, size_t num_objects,
                                    const uint8_t *coeffs_dev, size_t n, uint8_t *pieces_dev, const void *plan_dev);
+
+/* What rlnc_encode_emit writes in object_dev for a packet index at or beyond the emitted count. */
+#define RLNC_EMIT_NONE (-1)
+/* Bytes of rlnc_encode_emit's plan buffer: two int32 arrays of num_objects entries (an object's first packet, its
+ * grant), the sums of the chunks of 1,024 objects and the total, each rounded up to 16 bytes, and for
+ * max_per_object >= 4 the block-address streams of the product, ceil(max_per_object / tile rows) x k x tile rows
+ * entries of 8 bytes per object (tile rows = 8, 16, 32 or 64: the program of max_per_object rows) plus 512.  A
+ * multiple of 16, non-decreasing in each argument inside the limits; 0 when an argument is 0, k > 4,096,
+ * max_per_object > 4,096, num_objects > 1,048,576 or n > 1,048,576.  Pure: needs no context and no GPU. */
+size_t rlnc_encode_emit_plan_bytes(size_t k, size_t max_per_object, size_t num_objects, size_t n);
+/* The sender's call: want_dev[o] coded pieces per object, read on the device, written as one packed run of packets
+ * with an object id per packet and a device-side count.  (out_dev, object_dev, count_dev) go into
+ * rlnc_decode_stream_accept(arrivals_dev, object_dev, ..., count_dev) unchanged, so that emit -> wire -> (accept, push,
+ * deliver, compact) runs with no host decision on either end.  src_dev is [obj][k][L] with src_obj_stride bytes between
+ * objects (0 = k*L); r_dev is uint8 [n][k], packet i's random bytes: the random bytes are indexed by packet, not by
+ * object, so a caller supplies n x k bytes whatever the split.  n is the host-known packet capacity of out_dev,
+ * object_dev and r_dev.  Packet i starts at out_dev + i * out_stride (0 = k + L), at any byte address.
+ *   Let w_o = min(max(want_dev[o], 0), max_per_object), each entry read once; base_o = min(sum of w_o' for o' < o, n)
+ *   (object-major order); g_o = min(w_o, n - base_o); total = min(sum of w_o, n).  Every running sum saturates at n:
+ *   with n <= 2^20 and w <= 4,096 no sum needs more than int32.
+ *   Packet i with base_o <= i < base_o + g_o belongs to object o: object_dev[i] = o, out[i][0..k) = r_dev[i][0..k),
+ *   out[i][k..k+L) = XOR_j r_dev[i][j] . src[o][j][0..L).
+ *   object_dev[i] = RLNC_EMIT_NONE for total <= i < n; every entry of object_dev is written.  *count_dev = total.
+ *   granted_dev (int32 [num_objects], may be NULL): granted_dev[o] = g_o.
+ * Truncation: when the wants exceed n the low-numbered objects are served first and granted_dev says who was cut;
+ * fairness under truncation is the caller's (e.g. subtract granted from want and call again).
+ * Equivalence: byte for byte packet i is Encoder::code_with_buf of object o with the random bytes r_dev[i]
+ * (encoder.rs:241-250), and what rlnc_encode_batch writes for that coding vector.
+ * Footprint.  Written: the k + L bytes of packets [0, total); object_dev[0 .. n); *count_dev; granted_dev[0 ..
+ * num_objects); the plan buffer.  Never written: any byte of out_dev from packet total on; the bytes between k + L and
+ * out_stride; src_dev, want_dev, r_dev (rows of r_dev at or beyond total are not read either).  plan_dev is caller-owned
+ * scratch, 16-byte aligned and at least rlnc_encode_emit_plan_bytes long; its contents after the call are unspecified.
+ * Launches: at most six on the context's stream -- scan (a workgroup per 1,024 objects: w_o and its prefix inside the
+ * chunk), base (one workgroup: the prefix over the chunk sums, base_o, g_o, granted_dev, *count_dev; no atomics, no
+ * workgroup waits for another, so the split is deterministic), label (object_dev and the k header bytes), the
+ * block-address streams of the objects with g_o >= 4, the bit-sliced product over the whole 4 KiB column blocks of L
+ * (objects x row tiles x column blocks; the program of max_per_object rows serves the whole call, so a sender in its
+ * late rounds passes a small max_per_object), and the perm product over the rest: L mod 4,096, all of L for objects
+ * with 1 <= g_o < 4 (the tile programs take products of >= 4 rows; the grant is known on the device only) and for
+ * every object when the operands are not the program's (a row stride of 2^32 or more; misaligned operands where
+ * rlnc_device_unaligned_vector_access is 0).  The call never synchronises and grows no context workspace, but for the
+ * shared programs' one block-table probe per device: the call can be captured after one eager call on the device, as
+ * deliver and recode; a first call inside a capture runs every column in the perm product, the same bytes.
+ * Checks, in rlnc_encode_batch's order first: a null handle RLNC_ERR_INVALID_ARGUMENT; k == 0 PieceCountZero; L == 0
+ * PieceLengthZero; n == 0, num_objects == 0 or max_per_object == 0 RLNC_OK, nothing launched and nothing written; then
+ * k <= 4,096; max_per_object <= 4,096; n <= 1,048,576; num_objects <= 1,048,576; L <= 2^40; out_stride 0 or in
+ * [k + L, 2^42]; src_obj_stride 0 or >= k*L (and num_objects * src_obj_stride within 2^62); src_dev, want_dev, r_dev, out_dev, object_dev and count_dev non-null;
+ * plan_dev non-null, aligned and long enough; every launch within 2^31 - 1 workgroups.  Each failure is
+ * RLNC_ERR_INVALID_ARGUMENT, names the limit in rlnc_last_error and writes nothing.  Measurements: DESIGN.md §4.2.5. */
+int rlnc_encode_emit(rlnc_context *ctx, const uint8_t *src_dev, size_t src_obj_stride, size_t k, size_t L,
+                     size_t num_objects, const int32_t *want_dev, size_t max_per_object, const uint8_t *r_dev, size_t n,
+                     uint8_t *out_dev, size_t out_stride, int32_t *object_dev, int32_t *count_dev,
+                     int32_t *granted_dev, void *plan_dev, size_t plan_bytes);
+
 /* count recoded pieces per object from n received pieces: r [obj][count][n] → out [obj][count][k+L]
  * (recoder.rs:122-153; coefficient header and data are one linear combination of the full pieces). */
 int rlnc_recode_batch(rlnc_context *ctx, const uint8_t *pieces_dev, size_t k, size_t L, size_t n,
@@ -656,7 +710,8 @@ size_t rlnc_decode_stream_accept_plan_bytes(size_t n, size_t num_objects);
  * NULL; otherwise it points to one device int32, read by the rank and the base launch and written by neither, and the
  * call takes the first n' = min(max(*count_dev, 0), n)
  * arrivals (NULL: n' = n), so that a captured call replays with another number of arrivals each time.  n is the
- * host-known capacity, at most 1,048,576: a receiver with more arrivals calls again.  avail_dev (int32 [num_objects]) is
+ * host-known capacity, at most 1,048,576: a receiver with more arrivals calls again.  What rlnc_encode_emit writes as
+ * (out_dev, object_dev, count_dev) goes in as (arrivals_dev, object_dev, count_dev) unchanged.  avail_dev (int32 [num_objects]) is
  * the array push takes, and what rlnc_decode_stream_compact writes as answered_dev goes in as it is.  Per object o:
  *   let a = min(max(avail_dev[o], 0), m), read once, and i_0 < i_1 < ... the arrivals below n' whose id is o, in
  *   arrival order (the assignment is stable: no slot is claimed with an atomic).

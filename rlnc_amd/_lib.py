@@ -72,6 +72,8 @@ RLNC_ACCEPT_NO_ROOM = -1
 RLNC_ACCEPT_NO_OBJECT = -2
 RLNC_ACCEPT_FINISHED = -3
 RLNC_ACCEPT_ABSENT = -4
+# what rlnc_encode_emit writes in object_dev at or beyond the emitted count
+RLNC_EMIT_NONE = -1
 # which kernels a decode stream's push runs (rlnc_set_stream_form)
 RLNC_STREAM_FORM_AUTO = 0
 RLNC_STREAM_FORM_WORKSPACE = 1
@@ -146,6 +148,9 @@ _SIGS = {
                                             C.c_size_t]),
     "rlnc_encode_batch_data_planned": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp,
                                                  vp]),
+    "rlnc_encode_emit_plan_bytes": (C.c_size_t, [C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]),
+    "rlnc_encode_emit": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp, C.c_size_t, vp,
+                                   C.c_size_t, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]),
     "rlnc_decode_batch_eliminate": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t,
                                               vp, vp, vp]),
     "rlnc_decode_batch_apply": (C.c_int, [vp, vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t, vp,

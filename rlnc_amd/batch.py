@@ -702,3 +702,80 @@ class DecodeStream:
                                               C.c_void_p(pieces.data_ptr()), obj_stride, self.k, L, self.m,
                                               self.num_objects, av, sl, rf,
                                               C.c_void_p(self._accept_plan.data_ptr()), self._accept_plan.numel()), c.lib)
+
+
+def encode_emit_plan_bytes(k: int, max_per_object: int, num_objects: int, n: int) -> int:
+    """Device bytes of EncodeEmitter's plan buffer (rlnc_encode_emit_plan_bytes): a multiple of 16, non-decreasing in
+    each argument inside the limits, 0 for a zero argument, k > 4096, max_per_object > 4096, num_objects > 1,048,576
+    and n > 1,048,576.  Needs no GPU."""
+    from ._lib import load
+
+    return int(load().rlnc_encode_emit_plan_bytes(k, max_per_object, num_objects, n))
+
+
+class EncodeEmitter:
+    """The sender's side of a decode stream (rlnc_encode_emit): per-object piece counts read on the device, coded
+    pieces written as one packed run of packets with an object id per packet and a device-side count -- what
+    DecodeStream.accept takes as (arrivals, objects, count=count).
+
+    k, L: the generation; num_objects objects; max_per_object: the cap of one object's packets per call, which also
+    selects the product's program for the whole call (a sender in its late rounds builds an emitter with a small cap);
+    n: the packet capacity of out / objects / r.  The emitter owns the plan buffer, allocated here and never inside a
+    capture.  ctx=None: the default context of torch's current stream, created on first use -- a capture on a stream
+    that has none yet takes a context made beforehand.  emit launches on torch's current stream and never synchronises;
+    call it once eagerly before capturing it into a graph (that call looks up the 32- and 64-row programs' block table,
+    which a capture cannot; a first call inside a capture runs every column in the slower perm product, the same
+    bytes)."""
+
+    def __init__(self, k: int, L: int, num_objects: int, max_per_object: int, n: int, ctx: Context | None = None):
+        self.k, self.L, self.num_objects = int(k), int(L), int(num_objects)
+        self.max_per_object, self.n = int(max_per_object), int(n)
+        nbytes = encode_emit_plan_bytes(self.k, self.max_per_object, self.num_objects, self.n)
+        assert nbytes > 0 and self.L >= 1, \
+            f"an emit takes 1 <= k <= 4096, L >= 1, 1 <= max_per_object <= 4096, 1 <= num_objects <= 1,048,576 and " \
+            f"1 <= n <= 1,048,576: {(k, L, num_objects, max_per_object, n)}"
+        import torch
+
+        assert not torch.cuda.is_current_stream_capturing(), "the emit's plan buffer cannot be allocated inside a capture"
+        self.ctx = ctx
+        dev = torch.device("cuda", ctx.device if ctx is not None else torch.cuda.current_device())
+        self._plan = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+        assert self._plan.data_ptr() % 16 == 0
+
+    def _i32(self, t, shape, name):
+        import torch
+
+        assert t.dtype == torch.int32 and t.is_contiguous() and tuple(t.shape) == tuple(shape) and t.is_cuda, \
+            f"{name}: int32 contiguous device tensor of shape {tuple(shape)} required"
+        return C.c_void_p(t.data_ptr())
+
+    def emit(self, src, want, r, out, objects, count, granted=None) -> None:
+        """src uint8 [obj][k][L] on the device (stride(2) == 1, rows k*L-dense, any object stride >= k*L); want int32
+        [obj]: object o gets w = min(max(want[o], 0), max_per_object) packets, in object order, while the n packets
+        last (the low-numbered objects first); r uint8 [n][k], packet i's random bytes; out uint8 [n][k+L] with any row
+        stride >= k+L at any byte address: packet i = r[i] || sum_j r[i][j] * src[o][j]; objects int32 [n]: packet i's
+        object, RLNC_EMIT_NONE (-1) from the emitted count on; count int32 [1]: the emitted count; granted int32 [obj],
+        optional: the packets each object got.  No byte of out from packet count on is written.  (out, objects, count)
+        go to the transport, or straight into DecodeStream.accept(out, objects, pieces, avail, count=count)."""
+        import torch
+
+        k, L, nobj, n = self.k, self.L, self.num_objects, self.n
+        assert src.dtype == torch.uint8 and tuple(src.shape) == (nobj, k, L), (tuple(src.shape), (nobj, k, L))
+        assert (L == 1 or src.stride(2) == 1) and (k == 1 or src.stride(1) == L) and \
+            (nobj == 1 or src.stride(0) >= k * L), src.stride()
+        src_obj_stride = int(src.stride(0)) if nobj > 1 else k * L
+        assert r.dtype == torch.uint8 and tuple(r.shape) == (n, k) and r.is_contiguous(), (tuple(r.shape), (n, k))
+        S = k + L
+        assert out.dtype == torch.uint8 and tuple(out.shape) == (n, S), (tuple(out.shape), (n, S))
+        assert out.stride(1) == 1 and (n == 1 or out.stride(0) >= S), out.stride()
+        out_stride = int(out.stride(0)) if n > 1 else S
+        assert src.is_cuda and r.is_cuda and out.is_cuda, "src, r, out: device tensors required"
+        wt = self._i32(want, (nobj,), "want")
+        ob = self._i32(objects, (n,), "objects")
+        ct = self._i32(count, (1,), "count")
+        gr = self._i32(granted, (nobj,), "granted") if granted is not None else None
+        c = _ctx_for(self._plan, self.ctx)
+        check(c.lib.rlnc_encode_emit(c.h, C.c_void_p(src.data_ptr()), src_obj_stride, k, L, nobj, wt,
+                                     self.max_per_object, C.c_void_p(r.data_ptr()), n, C.c_void_p(out.data_ptr()),
+                                     out_stride, ob, ct, gr, C.c_void_p(self._plan.data_ptr()), self._plan.numel()),
+              c.lib)

@@ -40,6 +40,8 @@ pub const RLNC_ACCEPT_NO_ROOM: c_int = -1;
 pub const RLNC_ACCEPT_NO_OBJECT: c_int = -2;
 pub const RLNC_ACCEPT_FINISHED: c_int = -3;
 pub const RLNC_ACCEPT_ABSENT: c_int = -4;
+// what rlnc_encode_emit writes in object_dev at or beyond the emitted count
+pub const RLNC_EMIT_NONE: c_int = -1;
 // which kernels a decode stream's push runs (rlnc_set_stream_form)
 pub const RLNC_STREAM_FORM_AUTO: c_int = 0;
 pub const RLNC_STREAM_FORM_WORKSPACE: c_int = 1;
@@ -374,6 +376,28 @@ unsafe extern "C" {
         n: usize,
         pieces_dev: *mut u8,
         plan_dev: *const c_void,
+    ) -> c_int;
+    // the sender's emit: want_dev[o] pieces per object, packed out with ids and a count for
+    // rlnc_decode_stream_accept
+    pub fn rlnc_encode_emit_plan_bytes(k: usize, max_per_object: usize, num_objects: usize, n: usize) -> usize;
+    pub fn rlnc_encode_emit(
+        ctx: *mut rlnc_context,
+        src_dev: *const u8,
+        src_obj_stride: usize,
+        k: usize,
+        L: usize,
+        num_objects: usize,
+        want_dev: *const i32,
+        max_per_object: usize,
+        r_dev: *const u8,
+        n: usize,
+        out_dev: *mut u8,
+        out_stride: usize,
+        object_dev: *mut i32,
+        count_dev: *mut i32,
+        granted_dev: *mut i32,
+        plan_dev: *mut c_void,
+        plan_bytes: usize,
     ) -> c_int;
     pub fn rlnc_recode_batch(
         ctx: *mut rlnc_context,
