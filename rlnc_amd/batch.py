@@ -523,7 +523,8 @@ class DecodeStream:
     def push(self, pieces, avail, max_new: int | None = None, rank=None, answered=None) -> None:
         """Object o advances from the slots answered so far, done_o, to min(max(avail[o], done_o), m, done_o +
         max_new) (max_new=None: m).  avail may be overwritten as soon as this returns.  rank / answered (int32 [obj]
-        device tensors, optional) receive every object's rank and done_o after the push."""
+        device tensors, optional) receive every object's rank and done_o after the push; with max_new=0 nothing is launched
+        and neither is written."""
         L, obj_stride = self._pieces(pieces)
         n = (self.num_objects,)
         av = self._i32(avail, n, "avail")

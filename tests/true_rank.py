@@ -13,43 +13,79 @@ FIXTURE_K = 6
 FIXTURE = np.array([[0, 0, 2, 0, 0, 3], [0, 0, 0, 2, 2, 0], [0, 0, 0, 0, 0, 2], [0, 0, 0, 0, 0, 1]], np.uint8)
 
 
+class TrueRank:
+    """The normative steps on rows [c | e], e one byte per pushed piece, one piece at a time: a decoder that has room
+    for `slots` pieces.  true_rank_model is this class fed a whole list; the session model (tests/session_model.py)
+    keeps one per object, so that a push costs its new pieces only."""
+
+    def __init__(self, k, slots):
+        self.k, self.slots = k, slots
+        self.R = np.zeros((k, k + slots), np.uint8)  # the stored rows, in the order they were made
+        self.piv, self.st = [], []
+
+    def push(self, h):
+        k, p = self.k, len(self.st)
+        assert p < self.slots
+        h = np.asarray(h, np.uint8).reshape(k)
+        n = len(self.piv)
+        if n == k:  # step 1
+            self.st.append(RECEIVED_ALL)
+            return RECEIVED_ALL
+        v = np.zeros(k + self.slots, np.uint8)  # step 2
+        v[:k] = h
+        v[k + p] = 1
+        if n:  # v ^= h[pivot of r] * r for every stored row r, all rows at once
+            v ^= np.bitwise_xor.reduce(MUL[h[self.piv][:, None], self.R[:n]], axis=0)
+        nz = np.nonzero(v[:k])[0]
+        if nz.size == 0:  # step 3
+            self.st.append(NOT_USEFUL)
+            return NOT_USEFUL
+        pc = int(nz[0])  # step 4
+        v = MUL[npo.gf_inv(int(v[pc]))][v]
+        if n:  # r ^= r[pc] * v for every stored row r
+            self.R[:n] ^= MUL[self.R[:n, pc][:, None], v[None, :]]
+        self.R[n] = v
+        self.piv.append(pc)
+        self.st.append(OK)
+        return OK
+
+    @property
+    def rank(self):
+        return len(self.piv)
+
+    def result(self):
+        """(statuses, rank, T [k][pushed], C [rank][k]): T / C rows in pivot order, T rows >= rank zero."""
+        k, n = self.k, len(self.st)
+        T = np.zeros((k, n), np.uint8)
+        Cm = np.zeros((self.rank, k), np.uint8)
+        for i, r in enumerate(np.argsort(self.piv, kind="stable")):
+            T[i] = self.R[r][k: k + n]
+            Cm[i] = self.R[r][:k]
+        return list(self.st), self.rank, T, Cm
+
+    def gathered(self, u):
+        """The decoder of the pieces u_0 < u_1 < ... alone, u the Ok slots: a useless piece left a zero column of e in
+        every row, and the rows are the unique reduced rows of the span, so the columns are renumbered and nothing is
+        eliminated again (include/rlnc_hip.h, rlnc_decode_stream_compact, "Equivalence").
+        tests/test_stream_session_host.py holds every such decoder to one fed the kept vectors from scratch."""
+        k = self.k
+        assert list(u) == [t for t, s in enumerate(self.st) if s == OK]
+        out = TrueRank(k, self.slots)
+        n = len(self.piv)
+        out.R[:n, :k] = self.R[:n, :k]
+        out.R[:n, k: k + len(u)] = self.R[:n, k:][:, list(u)]
+        out.piv, out.st = list(self.piv), [OK] * len(u)
+        return out
+
+
 def true_rank_model(k, vectors):
     """The normative steps on rows [c | e], e one byte per pushed piece.  Returns (statuses, rank, T [k][m],
     C [rank][k]): T / C rows in pivot order, T rows >= rank zero."""
     vectors = np.asarray(vectors, np.uint8).reshape(-1, k)
-    m = vectors.shape[0]
-    rows, piv, st = [], [], []
-    for p, h in enumerate(vectors):
-        if len(rows) == k:  # step 1
-            st.append(RECEIVED_ALL)
-            continue
-        v = np.zeros(k + m, np.uint8)  # step 2
-        v[:k] = h
-        v[k + p] = 1
-        for r, pc in zip(rows, piv):
-            q = int(h[pc])
-            if q:
-                v ^= MUL[q][r]
-        nz = np.nonzero(v[:k])[0]
-        if nz.size == 0:  # step 3
-            st.append(NOT_USEFUL)
-            continue
-        pc = int(nz[0])  # step 4
-        v = MUL[npo.gf_inv(int(v[pc]))][v]
-        for r in rows:
-            q = int(r[pc])
-            if q:
-                r ^= MUL[q][v]
-        rows.append(v)
-        piv.append(pc)
-        st.append(OK)
-    rank = len(rows)
-    T = np.zeros((k, m), np.uint8)
-    Cm = np.zeros((rank, k), np.uint8)
-    for i, r in enumerate(np.argsort(piv, kind="stable")):
-        T[i] = rows[r][k:]
-        Cm[i] = rows[r][:k]
-    return st, rank, T, Cm
+    d = TrueRank(k, vectors.shape[0])
+    for h in vectors:
+        d.push(h)
+    return d.result()
 
 
 def sparse_vectors(rng, k, n, density):
